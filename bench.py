@@ -1,7 +1,14 @@
 """Benchmark: env.steps/s of batched CartPole worlds on MI355X (BASELINE.json config 2).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--worlds 4096]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--worlds 4096] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the headline line.
+--dump-outputs DIR also writes what the last timed step returned (obs, reward,
+done, terminal_obs) as DIR/<name>.npy.  --full adds every other measurement:
+the launch floor, the fused rollout, the world sweep, the other BASELINE
+configs' legs, the CPU baselines and the parity check (each `--no-*` switch
+drops one of them again).
 
 One "step" = one gym step of EVERY world of a rank: the action is applied, the
 physics runs (ABA + semi-implicit Euler, dt = 1 ms), and observation, reward,
@@ -15,7 +22,8 @@ over RCCL, as the north star asks.
 
 Printed JSON (rank 0): value = total env.steps/s over all ranks; roofline of
 the dominant kernel from per-launch HIP-event timing on its own stream;
-cpu_baseline = the fp64 C oracle on a bounded sample (rank 0, N = 1 only).
+with --full, cpu_baseline = the fp64 C oracle on a bounded sample (rank 0,
+N = 1 only) and one entry per leg; those fields are null in a plain run.
 """
 
 import argparse
@@ -67,7 +75,21 @@ def parse():
                    help="skip the projected 8-GPU strong split of configs 4 / 5 (their rank shares timed alone)")
     p.add_argument("--groups", type=int, default=1,
                    help="world groups per GPU, each on its own stream / hardware queue")
-    return p.parse_args()
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline: launch floor, fused rollout, world sweep, "
+                        "the other configs' legs, CPU baselines, parity check")
+    args = p.parse_args()
+    if not args.full:
+        for leg in FULL_ONLY:
+            setattr(args, "no_" + leg, True)
+    return args
+
+
+# what only a --full run measures; each has its --no-* switch
+FULL_ONLY = ("cpu_baseline", "rollout", "sweep", "panda", "rand_leg", "pendulum", "contact_leg", "runtime_leg",
+             "scene_leg", "free_legs", "pgs_leg", "share_proj")
 
 
 def main():
@@ -127,7 +149,9 @@ def main():
     achieved_gbs = bpe * W / (step_us * 1e-6) / 1e9
     event_gbs = bpe * W / (kernel_us * 1e-6) / 1e9
     traffic = pmc_traffic(args.task, W)
-    floor_us = launch_floor(dev, torch) if rank == 0 else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, timed["outputs"], np)
+    floor_us = launch_floor(dev, torch) if rank == 0 and args.full else None
 
     # ------------------------------------------- fused open-loop rollout figure
     rollout = None
@@ -493,7 +517,28 @@ def time_steps(envs, actions, warmup, K, chunk, dev, torch, dist, world_size, ga
             "stream": groups[0][1], "groups": S,
             "gathered_obs_shape": list(gathered.shape) if gather else None,
             "final_obs_sha256": hashlib.sha256(final.detach().cpu().contiguous().numpy().tobytes()).hexdigest(),
-            "final_obs": torch.cat([g[0].obs for g in groups]) if S > 1 else groups[0][0].obs}
+            "final_obs": torch.cat([g[0].obs for g in groups]) if S > 1 else groups[0][0].obs,
+            # what step() returns to its caller after the last timed step, this rank's worlds in order
+            "outputs": {name: torch.cat([getattr(g[0], name) for g in groups])
+                        for name in ("obs", "reward", "done", "terminal_obs")}}
+
+
+def dump_outputs(path, outputs, np):
+    """Write the last timed step's outputs (this rank's worlds) as path/<name>.npy,
+    float32; `done` (0 / 1 bytes on the device) is widened to float32 too.
+    Above 64 MB in all, the same seeded sample of worlds (worlds.npy) is kept
+    of every array."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {name: t.detach().cpu().numpy().astype(np.float32) for name, t in outputs.items()}
+    W = len(arrays["obs"])
+    row_bytes = sum(a.nbytes for a in arrays.values()) // W + 8
+    keep = 64_000_000 // row_bytes
+    if W > keep:
+        worlds = np.sort(np.random.default_rng(0).choice(W, keep, replace=False))
+        arrays = {name: a[worlds] for name, a in arrays.items()}
+        arrays["worlds"] = worlds.astype(np.float32 if W < (1 << 24) else np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 _HIP = None

@@ -23,12 +23,12 @@ timeout -k 10 150 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smo
 rc=$?; echo "smoke rc=$rc" | tee -a "$OUT/session.log"; tail -3 "$OUT/smoke_$tag.log"
 stop_if_fatal $rc smoke
 echo "== bench" | tee -a "$OUT/session.log"
-timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err"
+timeout -k 10 300 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err"
 rc=$?; echo "bench rc=$rc" | tee -a "$OUT/session.log"; cat "$OUT/bench_$tag.json"; tail -3 "$OUT/bench_$tag.err"
 stop_if_fatal $rc bench
 echo "== rocprofv3" | tee -a "$OUT/session.log"
 timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$OUT/prof_$tag" -o run --output-format csv -- \
-  python3 bench.py --steps 1000 --warmup 100 --no-cpu-baseline > "$OUT/bench_prof_$tag.json" 2> "$OUT/prof_$tag.err"
+  python3 bench.py --steps 1000 --warmup 100 --full --no-cpu-baseline > "$OUT/bench_prof_$tag.json" 2> "$OUT/prof_$tag.err"
 rc=$?; echo "rocprof rc=$rc" | tee -a "$OUT/session.log"; tail -3 "$OUT/prof_$tag.err"
 find "$OUT/prof_$tag" -name "*stats*" | head
 stop_if_fatal $rc rocprof

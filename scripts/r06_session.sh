@@ -16,7 +16,7 @@ echo "== smoke" | tee -a "$OUT/session_$tag.log"
 timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke_$tag.log" 2>&1
 rc=$?; echo "smoke rc=$rc" | tee -a "$OUT/session_$tag.log"; tail -2 "$OUT/smoke_$tag.log"; fatal $rc smoke
 echo "== bench" | tee -a "$OUT/session_$tag.log"
-timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err"
+timeout -k 10 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err"
 rc=$?; echo "bench rc=$rc" | tee -a "$OUT/session_$tag.log"; tail -c 600 "$OUT/bench_$tag.json"; fatal $rc bench
 if [ "${TRACE:-1}" = "1" ]; then
   # the driver's own command under the kernel tracer (no counters): the timed

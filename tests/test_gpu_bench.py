@@ -1,13 +1,16 @@
-"""The driver's exact bench command (`python bench.py --gpus 1 --steps 20
---warmup 5`) in a fresh process: one JSON line with the contract's fields,
-`roofline`, `cpu_baseline` and the parity figure (the r01 bench
-crashed on exactly this command because a leg was sized from --steps)."""
+"""The driver's bench commands in fresh processes.  `python bench.py --gpus 1
+--steps 20 --warmup 5 --full`: one JSON line with the contract's fields,
+`roofline`, `cpu_baseline`, the parity figure and every leg (the
+r01 bench crashed on this command because a leg was sized from --steps).  The
+plain command (no --full): the headline alone, and with --dump-outputs the
+last timed step's outputs, identical from run to run."""
 
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -18,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.timeout(600)
 def test_driver_bench_command(require_gpu):
     env = dict(os.environ)
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5"],
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "20", "--warmup", "5", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=560, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -58,3 +61,54 @@ def test_driver_bench_command(require_gpu):
         ps = out[leg]["projected_split"]
         assert ps["n_gpus"] == 8 and ps["worlds_per_gpu"] == wg // 8 and len(ps["share_ms_per_step"]) == 8, leg
         assert ps["ms_per_step"] == max(ps["share_ms_per_step"]) and ps["speedup_vs_1gpu"] > 0, leg
+
+
+LEGS = ("world_sweep", "cpu_baseline", "obs_max_abs_err_vs_oracle", "rollout_fused", "panda_c4", "pendulum_c3",
+        "randomized", "contacts_floating", "quadruped_floating", "humanoid_c5", "humanoid_c5_pgs_only",
+        "runtime_c1", "scene_multi_model")
+
+
+def _plain_run(out_dir):
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "30", "--warmup", "5",
+                        "--graph-chunk", "20", "--dump-outputs", str(out_dir)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0]), {f[:-4]: np.load(os.path.join(out_dir, f)) for f in sorted(os.listdir(out_dir))}
+
+
+@pytest.fixture(scope="module")
+def plain_run(require_gpu, tmp_path_factory):
+    return _plain_run(tmp_path_factory.mktemp("bench_a"))
+
+
+def test_plain_run_is_the_headline_alone(plain_run):
+    """Without --full: the contract's fields with today's meaning, no leg, no
+    CPU baseline, no launch floor; --steps is the number of timed steps (two
+    graphs here: 20 + 10) and ms_per_step the time of one of them."""
+    out, arrays = plain_run
+    assert out["steps"] == 30 and out["warmup"] == 5 and out["n_gpus"] == 1
+    assert out["unit"] == "env\u00b7steps/s" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["value"] == pytest.approx(4096 / (out["ms_per_step"] * 1e-3), rel=1e-3) and out["value"] > 1e6
+    assert out["roofline"]["bound"] == "hbm" and 0 < out["roofline"]["frac"] < 1
+    assert out["roofline"]["launch_floor_us"] is None
+    for leg in LEGS:
+        assert out[leg] is None, leg
+    assert sorted(arrays) == ["done", "obs", "reward", "terminal_obs"]
+    assert arrays["obs"].shape == (4096, 4) and arrays["terminal_obs"].shape == (4096, 4)
+    assert arrays["reward"].shape == (4096,) and arrays["done"].shape == (4096,)
+    for name, a in arrays.items():
+        assert a.dtype == np.float32 and np.isfinite(a).all(), name
+    assert np.abs(arrays["obs"]).max() > 0 and set(np.unique(arrays["done"])) <= {0.0, 1.0}
+    import hashlib
+    assert hashlib.sha256(arrays["obs"].tobytes()).hexdigest() == out["final_obs_sha256"]
+
+
+def test_dumped_outputs_repeat(plain_run, tmp_path):
+    """The same arguments give the same inputs, so a second run of the same
+    build writes the same arrays bit for bit."""
+    _, first = plain_run
+    _, second = _plain_run(tmp_path)
+    for name, a in first.items():
+        assert np.array_equal(a, second[name]), name

@@ -30,7 +30,7 @@ def _bench(n_ranks, worlds):
     args = [os.path.join(ROOT, "bench.py"), "--gpus", str(n_ranks), "--steps", "20", "--warmup", "5",
             "--worlds", str(worlds), "--no-rollout", "--no-sweep", "--no-rand-leg", "--no-pendulum",
             "--no-runtime-leg", "--no-scene-leg", "--no-cpu-baseline", "--no-free-legs", "--no-pgs-leg",
-            "--no-share-proj"]
+            "--no-share-proj", "--full"]  # --full: the config-4 / config-5 legs
     if n_ranks > 1:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n_ranks),
                "--master-addr", "127.0.0.1", "--master-port", str(_free_port())] + args
