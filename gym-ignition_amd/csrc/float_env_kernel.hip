@@ -1,0 +1,222 @@
+// float_env_kernel.hip -- the device layer of the batched env for articulated
+// floating-base models on the world-per-wavefront kernel (mw_floatenv_create).
+// One env step is three launches on the sim's stream:
+//
+//   float_env_action_kernel   actions [W, n] -> SimDev::cmd / ptgt [n][W]
+//   wave_run_kernel           (kernels.hip, unchanged) one run of every world
+//   float_env_post_kernel     obs / reward / done, and for the done worlds the
+//                             pending resets the next run's first launch applies
+//
+// Both kernels are transposes between the row-major [W, k] tensors of the
+// agent and the [k][W] SoA arrays of the simulator.  A block of 256 threads
+// owns a tile of 64 worlds and stages it through LDS, so the row side moves
+// as contiguous spans and the SoA side with the world index across the lanes:
+// both global sides are coalesced.  Rows in LDS are `k | 1` words apart: a
+// lane-per-world access then strides an odd number of banks (conflict-free
+// for ds_read_b32 / ds_write_b32, whose banks are word address mod 32 within
+// each 32-lane half).
+#include <hip/hip_runtime.h>
+
+#include "finite.hpp"
+#include "float_task.hpp"
+#include "kernels.hpp"
+#include "rng.hpp"
+
+namespace mw {
+namespace dev {
+
+constexpr int kEnvTile = 64;      // worlds per block (lane = world)
+constexpr int kEnvThreads = 256;  // 4 waves share the tile's columns / rows
+constexpr int kEnvWaves = kEnvThreads / 64;
+
+// actions [W, n] -> out [n][W] (SimDev::cmd or ptgt), and sum_i a_i^2 per
+// world for the reward (asq [W]).  The value stored is the float32 the host
+// setters would upload for that number; the effort limit stays with the run
+// kernel's clamp, as on the host-commanded path.  That clamp (a min / max
+// pair) turns a NaN torque into -effort without a trace, and the PID drops a
+// NaN target: a world whose action holds a non-finite value is therefore
+// flagged diverged here (sticky flag + count, as the run kernels flag a
+// non-finite state), so that the post kernel ends and resets it.
+__global__ void __launch_bounds__(kEnvThreads) float_env_action_kernel(const float* __restrict__ actions,
+                                                                       float* __restrict__ out,
+                                                                       float* __restrict__ asq,
+                                                                       uint8_t* __restrict__ div,
+                                                                       unsigned long long* __restrict__ ndiv, int n,
+                                                                       int W) {
+    extern __shared__ float tile[];  // [kEnvTile][n | 1]
+    const int pitch = n | 1;
+    const int w0 = blockIdx.x * kEnvTile;
+    const int rows = min(kEnvTile, W - w0);
+    const float* __restrict__ src = actions + static_cast<size_t>(w0) * n;
+    // the tile's rows are one contiguous span of rows * n words
+    for (int i = threadIdx.x; i < rows * n; i += kEnvThreads) {
+        const int r = i / n, d = i - r * n;
+        tile[r * pitch + d] = src[i];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane >= rows) return;
+    const float* row = tile + lane * pitch;
+    for (int d = wave; d < n; d += kEnvWaves) out[static_cast<size_t>(d) * W + w0 + lane] = row[d];
+    if (wave == 0) {
+        asq[w0 + lane] = ft_sum_sq(row, n, 1);
+        bool bad = false;
+        for (int d = 0; d < n; ++d) bad = bad || nonfinite_bits(row[d]);
+        if (bad && !div[w0 + lane]) {
+            div[w0 + lane] = 1;
+            atomicAdd(ndiv, 1ull);
+        }
+    }
+}
+
+// Per world: gather the observation, reward, done, counters; where done, the
+// terminal observation, the reset sample written as pending resets (exactly
+// the bits and values mw_reset_joint_positions + mw_reset_joint_velocities +
+// mw_reset_base_pose + mw_reset_base_velocity leave on the device), the
+// divergence flag re-armed, and the reset state's observation.  reset_all:
+// every world starts episode 0 (mw_vecenv_reset), only obs is written.
+__global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const ChainF* __restrict__ P, FloatTaskF T,
+                                                                     SimDev S, FreeDev D, VecDev V,
+                                                                     const float* __restrict__ asq,
+                                                                     float* __restrict__ obs,
+                                                                     float* __restrict__ reward,
+                                                                     uint8_t* __restrict__ done_out,
+                                                                     float* __restrict__ term_obs, int n, int W,
+                                                                     int reset_all) {
+    extern __shared__ float tile[];  // [kEnvTile][n_obs | 1]: the observation rows
+    __shared__ uint8_t s_done[kEnvTile];
+    __shared__ uint32_t s_episode[kEnvTile];
+    const int NO = T.n_obs, pitch = NO | 1;
+    const int w0 = blockIdx.x * kEnvTile;
+    const int rows = min(kEnvTile, W - w0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int w = w0 + lane;
+    const bool live = lane < rows;
+    float* row = tile + lane * pitch;
+    const size_t Ws = static_cast<size_t>(W);
+    if (!reset_all) {
+        // gather: lane = world, the waves split the words
+        if (live) {
+            if (wave == 0) {
+                float b[13], lin[3], ang[3];
+#pragma unroll
+                for (int k = 0; k < 13; ++k) b[k] = D.base[k * Ws + w];
+                ft_world_velocity(b, lin, ang);
+#pragma unroll
+                for (int k = 0; k < 7; ++k) row[k] = b[k];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) { row[7 + k] = lin[k]; row[10 + k] = ang[k]; }
+            }
+            for (int k = wave; k < 2 * n; k += kEnvWaves)
+                row[13 + k] = (k < n) ? S.q[k * Ws + w] : S.qd[(k - n) * Ws + w];
+            for (int j = wave; j < T.n_links; j += kEnvWaves) {
+                // world z force of the link: its active contact slots of the last substep
+                float f = 0.f;
+                for (uint32_t m = D.cmask[w] & T.link_slots[j]; m; m &= m - 1u)
+                    f += D.cdata[(static_cast<size_t>(__builtin_ctz(m)) * 7 + 5) * Ws + w];
+                row[13 + 2 * n + j] = f;
+            }
+        }
+        __syncthreads();
+        if (wave == 0) {
+            bool done = false;
+            uint32_t episode = 0u;
+            if (live) {
+                const bool term = ft_terminated(row[2], ft_tilt(row[4], row[5]), S.div[w] != 0, T.z_min, T.cos_tilt_max);
+                uint32_t steps = V.steps[w] + 1u;
+                done = term || (T.max_steps > 0 && steps >= static_cast<uint32_t>(T.max_steps));
+                reward[w] = ft_reward(T, term, row[7], asq[w], ft_sum_sq_diff(row + 13, 1, T.home_q, n));
+                done_out[w] = done ? 1 : 0;
+                episode = V.episode[w];
+                if (done) {
+                    episode += 1u;
+                    steps = 0u;
+                    V.episode[w] = episode;
+                }
+                V.steps[w] = steps;
+            }
+            s_done[lane] = done ? 1 : 0;
+            s_episode[lane] = episode;
+        }
+        __syncthreads();
+        // the finished episodes' last observation: row r of the tile, lanes across its words
+        for (int r = wave; r < rows; r += kEnvWaves)
+            if (s_done[r])
+                for (int k = lane; k < NO; k += 64) term_obs[static_cast<size_t>(w0 + r) * NO + k] = tile[r * pitch + k];
+        __syncthreads();
+    } else {
+        if (wave == 0) {
+            s_done[lane] = live ? 1 : 0;
+            s_episode[lane] = 0u;
+            if (live) {
+                V.episode[w] = 0u;
+                V.steps[w] = 0u;
+            }
+        }
+        __syncthreads();
+    }
+    // resets: home pose + U(-noise, noise) per joint clipped into the position
+    // limits, Philox counter (global world, episode, block of 4 dofs, 0) as
+    // pid_task_reset; the base at home_base, everything at rest
+    if (live && s_done[lane]) {
+        const uint32_t episode = s_episode[lane];
+        for (int b = wave; b < (n + 3) / 4; b += kEnvWaves) {
+            uint32_t r[4];
+            philox(T.seed_lo, T.seed_hi, T.world_offset + static_cast<uint32_t>(w), episode, r, static_cast<uint32_t>(b));
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int d = 4 * b + k;
+                if (d < n) {
+                    const float x = T.home_q[d] + unif(r[k], -T.joint_noise, T.joint_noise);
+                    const float q = fminf(fmaxf(x, P->b[d].lower), P->b[d].upper);
+                    const size_t i = d * Ws + w;
+                    S.rq[i] = q;
+                    S.rqd[i] = 0.f;
+                    S.rflag[i] = 1u | 2u | 4u;  // position, velocity, PID reset
+                    row[13 + d] = q;
+                    row[13 + n + d] = 0.f;
+                }
+            }
+        }
+        if (wave == 0) {
+#pragma unroll
+            for (int k = 0; k < 7; ++k) {
+                D.rpose[k * Ws + w] = T.home_base[k];
+                row[k] = T.home_base[k];
+            }
+#pragma unroll
+            for (int k = 0; k < 6; ++k) {
+                D.rvel[k * Ws + w] = 0.f;
+                row[7 + k] = 0.f;
+            }
+            D.rflag[w] = 1u | 2u;
+            S.div[w] = 0;  // a reset re-arms the divergence flag (mw_reset_* do)
+        }
+        for (int j = wave; j < T.n_links; j += kEnvWaves) row[13 + 2 * n + j] = 0.f;
+    }
+    __syncthreads();
+    for (int r = wave; r < rows; r += kEnvWaves)
+        for (int k = lane; k < NO; k += 64) obs[static_cast<size_t>(w0 + r) * NO + k] = tile[r * pitch + k];
+}
+
+}  // namespace dev
+
+hipError_t launch_float_env_action(const float* actions, float* out, float* asq, uint8_t* div,
+                                   unsigned long long* ndiv, int n, int W, hipStream_t st) {
+    const size_t lds = static_cast<size_t>(dev::kEnvTile) * (n | 1) * sizeof(float);
+    hipLaunchKernelGGL(dev::float_env_action_kernel, dim3((W + dev::kEnvTile - 1) / dev::kEnvTile),
+                       dim3(dev::kEnvThreads), lds, st, actions, out, asq, div, ndiv, n, W);
+    return hipGetLastError();
+}
+
+hipError_t launch_float_env_post(const ChainF* P, const FloatTaskF& T, const SimDev& S, const FreeDev& D,
+                                 const VecDev& V, const float* asq, float* obs, float* reward, uint8_t* done,
+                                 float* term_obs, int n, int W, int reset_all, hipStream_t st) {
+    const size_t lds = static_cast<size_t>(dev::kEnvTile) * (T.n_obs | 1) * sizeof(float);
+    hipLaunchKernelGGL(dev::float_env_post_kernel, dim3((W + dev::kEnvTile - 1) / dev::kEnvTile),
+                       dim3(dev::kEnvThreads), lds, st, P, T, S, D, V, asq, obs, reward, done, term_obs, n, W,
+                       reset_all);
+    return hipGetLastError();
+}
+
+}  // namespace mw

@@ -1,0 +1,99 @@
+// float_task.hpp -- task arithmetic of the batched env for articulated
+// floating-base models (float_env_kernel.hip): world-frame base velocity from
+// the stored body twist, tilt, reward and the termination predicate, float32.
+// Plain inline functions: the post kernel calls them per world, and
+// tests/host_float_task/harness.cpp builds the same code with g++ against
+// numpy fp64.  The Philox reset sampling stays in rng.hpp (device only).
+#pragma once
+
+#ifdef MW_HOST_TEST
+#include <cmath>
+#ifndef __device__
+#define __device__
+#endif
+#ifndef __forceinline__
+#define __forceinline__ inline
+#endif
+#else
+#include <hip/hip_runtime.h>
+#endif
+
+#include <cstddef>
+#include <cstdint>
+
+#include "chain_params.hpp"
+
+namespace mw {
+
+constexpr int kMaxContactLinks = 8;  // mw_float_task_config::contact_links
+
+// Task description of the floating-base env (kernel argument, by value).
+struct FloatTaskF {
+    int32_t action_mode;     // 0 torque (SimDev::cmd), 1 position (SimDev::ptgt)
+    int32_t max_steps;       // 0 = no time limit
+    int32_t n_links;         // contact words of the observation
+    int32_t n_obs;           // 13 + 2 n + n_links
+    uint32_t seed_lo, seed_hi;
+    uint32_t world_offset;
+    float z_min, cos_tilt_max;
+    float alive_bonus, w_forward, w_action, w_pose;
+    float joint_noise;
+    float home_base[7];      // x y z qw qx qy qz
+    uint32_t link_slots[kMaxContactLinks];  // contact slots (FreeDev::cmask bits) of every contact link
+    float home_q[kMaxBodies];
+};
+
+namespace dev {
+
+// The rotation of the base (row-major, body -> world) from its unit
+// quaternion: the matrix mw_get_base_velocity rotates the body twist with.
+__device__ __forceinline__ void ft_rotation(float qw, float qx, float qy, float qz, float (&R)[9]) {
+    R[0] = 1.f - 2.f * (qy * qy + qz * qz); R[1] = 2.f * (qx * qy - qw * qz); R[2] = 2.f * (qx * qz + qw * qy);
+    R[3] = 2.f * (qx * qy + qw * qz); R[4] = 1.f - 2.f * (qx * qx + qz * qz); R[5] = 2.f * (qy * qz - qw * qx);
+    R[6] = 2.f * (qx * qz - qw * qy); R[7] = 2.f * (qy * qz + qw * qx); R[8] = 1.f - 2.f * (qx * qx + qy * qy);
+}
+
+// World linear velocity of the base origin and world angular velocity from
+// the stored base words [13] = p xyz, q wxyz, body twist w xyz, v xyz
+// (Model::baseWorldLinearVelocity / baseWorldAngularVelocity).
+__device__ __forceinline__ void ft_world_velocity(const float (&base)[13], float (&lin)[3], float (&ang)[3]) {
+    float R[9];
+    ft_rotation(base[3], base[4], base[5], base[6], R);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        lin[r] = R[3 * r] * base[10] + R[3 * r + 1] * base[11] + R[3 * r + 2] * base[12];
+        ang[r] = R[3 * r] * base[7] + R[3 * r + 1] * base[8] + R[3 * r + 2] * base[9];
+    }
+}
+
+// R_zz: the world-z component of the base's z axis (1 upright, 0 on its side).
+__device__ __forceinline__ float ft_tilt(float qx, float qy) { return 1.f - 2.f * (qx * qx + qy * qy); }
+
+// Terminated by height, tilt or divergence (the time limit is not a failure).
+__device__ __forceinline__ bool ft_terminated(float z, float rzz, bool diverged, float z_min, float cos_tilt_max) {
+    return z < z_min || rzz < cos_tilt_max || diverged;
+}
+
+// sum_i x_i^2 and sum_i (x_i - h_i)^2 over n values `stride` apart, in index order
+__device__ __forceinline__ float ft_sum_sq(const float* x, int n, size_t stride) {
+    float s = 0.f;
+    for (int i = 0; i < n; ++i) s += x[i * stride] * x[i * stride];
+    return s;
+}
+__device__ __forceinline__ float ft_sum_sq_diff(const float* x, size_t stride, const float* h, int n) {
+    float s = 0.f;
+    for (int i = 0; i < n; ++i) {
+        const float e = x[i * stride] - h[i];
+        s += e * e;
+    }
+    return s;
+}
+
+// alive_bonus [not terminated] + w_forward v_x - w_action sum a^2 - w_pose sum (q - home)^2
+__device__ __forceinline__ float ft_reward(const FloatTaskF& T, bool terminated, float vx, float sum_a2,
+                                           float sum_pose2) {
+    return (terminated ? 0.f : T.alive_bonus) + T.w_forward * vx - T.w_action * sum_a2 - T.w_pose * sum_pose2;
+}
+
+}  // namespace dev
+}  // namespace mw

@@ -156,6 +156,19 @@ hipError_t launch_vecenv_pid_group(const ChainF* P, int n, bool cons, bool dual,
                                    float* reward, uint8_t* done, float* term_obs, int W, float dt, int substeps,
                                    int pgs_iters, hipStream_t st);
 
+// Batched env of articulated floating-base models on the wave kernel
+// (float_env_kernel.hip; T: float_task.hpp).  The action launch transposes
+// actions float32 [W, n] into out [n][W] (SimDev::cmd or ptgt) and leaves
+// sum a^2 per world in asq [W], and flags a world whose action is not finite as
+// diverged (SimDev::div / ndiv); the post launch follows the run: obs / reward
+// / done / counters, and the done worlds' pending resets for the next run.
+// reset_all: every world starts episode 0, only obs is written.
+hipError_t launch_float_env_action(const float* actions, float* out, float* asq, uint8_t* div,
+                                   unsigned long long* ndiv, int n, int W, hipStream_t st);
+hipError_t launch_float_env_post(const ChainF* P, const struct FloatTaskF& T, const SimDev& S, const FreeDev& D,
+                                 const VecDev& V, const float* asq, float* obs, float* reward, uint8_t* done,
+                                 float* term_obs, int n, int W, int reset_all, hipStream_t st);
+
 // T_steps == 0: one step with the per-step output layout; otherwise a fused
 // open-loop rollout of T_steps steps ([T, W] inputs and outputs).
 // baked: id of a bit-identical shipped model (baked_models.hpp) or 0 (generic)

@@ -23,6 +23,7 @@
 
 #include "baked_models.hpp"
 #include "chain_params.hpp"
+#include "float_task.hpp"
 #include "float_tree.hpp"
 #include "free_body.hpp"
 #include "kernels.hpp"
@@ -64,6 +65,9 @@ struct mw_sim {
     bool stepped = false;     // model parameters become read-only after the first run
     bool servo_used = false;  // a joint was put in VelocityFollowerDart
     bool host_stale = false;  // device state changed by the VecEnv path
+    // a floating-base env (mw_floatenv_create) writes the commands and pending
+    // resets on the device: the host setters of either fail with MW_ESTATE
+    bool env_owned = false;
     bool cmd_dirty = true;
     bool ptgt_dirty = false;  // host position targets newer than the device copy
     bool ptgt_stale = false;  // device position targets newer than the host mirror
@@ -191,6 +195,10 @@ struct mw_vecenv {
     mw::GLaneTask* d_lane = nullptr;
     mw::GLaneTask h_lane[mw::kMaxKernelDofs] = {};
     bool lane_uploaded = false;
+    // floating-base env (mw_floatenv_create): its task and sum a^2 per world
+    bool floatenv = false;
+    mw::FloatTaskF ftask{};
+    float* d_asq = nullptr;
 };
 
 namespace {
@@ -198,6 +206,17 @@ namespace {
 int check_sim(const mw_sim* s, bool need_init = true) {
     if (!s) return fail(MW_EINVAL, "null simulator handle");
     if (need_init && !s->initialized) return fail(MW_ESTATE, "the simulator was not initialized");
+    return MW_OK;
+}
+
+// Host setters of commands / pending resets on a simulator that a
+// floating-base env drives: the env writes the same device arrays from its
+// kernels, and the staging copy of run_impl covers the whole command block, so
+// either side would silently lose the other's values.
+int check_not_env_owned(const mw_sim* s, const char* what) {
+    if (s && s->env_owned)
+        return fail(MW_ESTATE, std::string(what) + ": a floating-base env owns this simulator's commands and pending "
+                                                   "resets (they live on the device); destroy the env first");
     return MW_OK;
 }
 
@@ -1495,6 +1514,7 @@ int mw_get_joint_position_targets(const mw_sim* cs, int32_t w0, int32_t nw, cons
 }
 
 int mw_set_joint_force_targets(mw_sim* s, int32_t w0, int32_t nw, const int32_t* d, int32_t nd, const double* v) {
+    if (int own = check_not_env_owned(s, "mw_set_joint_force_targets")) return own;
     // Joint::setGeneralizedForceTarget, Joint.cpp:774-815: allowed in Force,
     // Position, PositionInterpolated and Velocity modes
     return setter(s, w0, nw, d, nd, v, [&](int dof, int w, double x, bool dry) {
@@ -1511,6 +1531,7 @@ int mw_set_joint_force_targets(mw_sim* s, int32_t w0, int32_t nw, const int32_t*
 }
 
 int mw_set_joint_velocity_targets(mw_sim* s, int32_t w0, int32_t nw, const int32_t* d, int32_t nd, const double* v) {
+    if (int own = check_not_env_owned(s, "mw_set_joint_velocity_targets")) return own;
     // Joint::setVelocityTarget, Joint.cpp:728-754
     return setter(s, w0, nw, d, nd, v, [&](int dof, int w, double x, bool dry) {
         const int m = s->mode[s->idx(dof, w)];
@@ -1522,6 +1543,7 @@ int mw_set_joint_velocity_targets(mw_sim* s, int32_t w0, int32_t nw, const int32
 }
 
 int mw_set_joint_position_targets(mw_sim* s, int32_t w0, int32_t nw, const int32_t* d, int32_t nd, const double* v) {
+    if (int own = check_not_env_owned(s, "mw_set_joint_position_targets")) return own;
     // Joint::setPositionTarget, Joint.cpp:694-726
     if (s && s->initialized) {
         int rc = pull_ptgt(s);
@@ -1542,6 +1564,7 @@ int mw_set_joint_position_targets(mw_sim* s, int32_t w0, int32_t nw, const int32
 }
 
 int mw_reset_joint_positions(mw_sim* s, int32_t w0, int32_t nw, const int32_t* d, int32_t nd, const double* v) {
+    if (int own = check_not_env_owned(s, "mw_reset_joint_positions")) return own;
     // Joint::resetPosition writes JointPositionReset, applied by the next run (Joint.cpp:132-156)
     const int rc = setter(s, w0, nw, d, nd, v, [&](int dof, int w, double x, bool dry) {
         if (!dry) {
@@ -1554,6 +1577,7 @@ int mw_reset_joint_positions(mw_sim* s, int32_t w0, int32_t nw, const int32_t* d
 }
 
 int mw_reset_joint_velocities(mw_sim* s, int32_t w0, int32_t nw, const int32_t* d, int32_t nd, const double* v) {
+    if (int own = check_not_env_owned(s, "mw_reset_joint_velocities")) return own;
     const int rc = setter(s, w0, nw, d, nd, v, [&](int dof, int w, double x, bool dry) {
         if (!dry) {
             s->hrqd()[s->idx(dof, w)] = static_cast<float>(x);
@@ -1565,6 +1589,7 @@ int mw_reset_joint_velocities(mw_sim* s, int32_t w0, int32_t nw, const int32_t* 
 }
 
 int mw_set_joint_control_mode(mw_sim* s, int32_t w0, int32_t nw, const int32_t* d, int32_t nd, int32_t mode) {
+    if (int own = check_not_env_owned(s, "mw_set_joint_control_mode")) return own;
     int rc = check_sim(s);
     if (rc) return rc;
     // Joint::setControlMode, Joint.cpp:369-460
@@ -1603,6 +1628,7 @@ int mw_set_joint_control_mode(mw_sim* s, int32_t w0, int32_t nw, const int32_t* 
 }
 
 int mw_set_joint_pid(mw_sim* s, int32_t dof, const double gains[8]) {
+    if (int own = check_not_env_owned(s, "mw_set_joint_pid")) return own;
     if (!s || !gains) return fail(MW_EINVAL, "null argument");
     if (!s->loaded) return fail(MW_ESTATE, "no model loaded");
     if (dof < 0 || dof >= s->n) return fail(MW_EINVAL, "dof out of range");
@@ -1746,6 +1772,7 @@ int mw_get_base_velocity(const mw_sim* cs, int32_t w0, int32_t nw, double* out) 
 }
 
 int mw_reset_base_pose(mw_sim* s, int32_t w0, int32_t nw, const double* in) {
+    if (int own = check_not_env_owned(s, "mw_reset_base_pose")) return own;
     int rc = check_free(s);
     if (rc) return rc;
     if (!in || w0 < 0 || nw < 0 || w0 + nw > s->W) return fail(MW_EINVAL, "bad world range or null input");
@@ -1765,6 +1792,7 @@ int mw_reset_base_pose(mw_sim* s, int32_t w0, int32_t nw, const double* in) {
 }
 
 int mw_reset_base_velocity(mw_sim* s, int32_t w0, int32_t nw, const double* in) {
+    if (int own = check_not_env_owned(s, "mw_reset_base_velocity")) return own;
     int rc = check_free(s);
     if (rc) return rc;
     if (!in || w0 < 0 || nw < 0 || w0 + nw > s->W) return fail(MW_EINVAL, "bad world range or null input");
@@ -2041,6 +2069,7 @@ int mw_get_state(mw_sim* s, int32_t w0, int32_t nw, float* out) {
 }
 
 int mw_set_state(mw_sim* s, int32_t w0, int32_t nw, const float* in) {
+    if (int own = check_not_env_owned(s, "mw_set_state")) return own;
     int rc = check_sim(s);
     if (rc) return rc;
     if (!in || w0 < 0 || nw < 0 || w0 + nw > s->W) return fail(MW_EINVAL, "bad argument");
@@ -2191,9 +2220,115 @@ int mw_vecenv_create(mw_sim* s, const mw_task_config* cfg, mw_vecenv** out) {
     return MW_OK;
 }
 
+// Batched env of an articulated floating-base model on the wave kernel
+// (float_env_kernel.hip): the env's kernels write the run kernel's command
+// and pending-reset arrays on the device, the run itself is run_impl's.
+int mw_floatenv_create(mw_sim* s, const mw_float_task_config* cfg, mw_vecenv** out) {
+    if (!s || !cfg || !out) return fail(MW_EINVAL, "null argument");
+    *out = nullptr;
+    int rc = check_sim(s);
+    if (rc) return rc;
+    if (!s->floating || !s->float_tree || !s->wave || s->n == 0)
+        return fail(MW_EINVAL, "the floating-base env needs an articulated model on a floating base (joints, "
+                               "mw_is_floating) stepped by the world-per-wavefront kernel (mw_float_kernel == 2)");
+    if (s->env_owned) return fail(MW_ESTATE, "the simulator already has a floating-base env");
+    const int n = s->n;
+    for (int d = 0; d < n; ++d)
+        if (s->model.bodies[d].ball)
+            return fail(MW_EINVAL, "the floating-base env does not take models with ball joints (joint '" +
+                                       s->model.bodies[d].joint_name + "')");
+    if (s->cfg.steps_per_run > 64) return fail(MW_EINVAL, "steps_per_run must be <= 64");
+    if (cfg->action_mode != MW_FLOAT_ACTION_TORQUE && cfg->action_mode != MW_FLOAT_ACTION_POSITION)
+        return fail(MW_EINVAL, "unknown action mode");
+    if (cfg->max_episode_steps < 0) return fail(MW_EINVAL, "max_episode_steps must be >= 0");
+    if (cfg->world_offset < 0) return fail(MW_EINVAL, "world_offset must be >= 0");
+    if (!cfg->home_q) return fail(MW_EINVAL, "home_q is null (one value per dof)");
+    if (cfg->n_contact_links < 0 || cfg->n_contact_links > mw::kMaxContactLinks)
+        return fail(MW_EINVAL, "n_contact_links must be in [0, " + std::to_string(mw::kMaxContactLinks) + "]");
+    if (cfg->n_contact_links > 0 && !cfg->contact_links) return fail(MW_EINVAL, "contact_links is null");
+    for (int j = 0; j < cfg->n_contact_links; ++j)
+        if (cfg->contact_links[j] < -1 || cfg->contact_links[j] >= n)
+            return fail(MW_EINVAL, "contact link " + std::to_string(cfg->contact_links[j]) + " out of range [-1, " +
+                                       std::to_string(n) + ")");
+    {
+        const float* hb = cfg->home_base;
+        if (!(hb[3] * hb[3] + hb[4] * hb[4] + hb[5] * hb[5] + hb[6] * hb[6] > 0.f))
+            return fail(MW_EINVAL, "the home_base orientation quaternion is zero");
+    }
+    if (!(cfg->joint_noise >= 0.f)) return fail(MW_EINVAL, "joint_noise must be >= 0");
+    auto e = std::make_unique<mw_vecenv>();
+    e->sim = s;
+    e->floatenv = true;
+    mw::FloatTaskF& T = e->ftask;
+    T.action_mode = cfg->action_mode;
+    T.max_steps = cfg->max_episode_steps;
+    T.n_links = cfg->n_contact_links;
+    T.n_obs = 13 + 2 * n + cfg->n_contact_links;
+    T.seed_lo = static_cast<uint32_t>(cfg->seed);
+    T.seed_hi = static_cast<uint32_t>(cfg->seed >> 32);
+    T.world_offset = static_cast<uint32_t>(cfg->world_offset);
+    T.z_min = cfg->z_min;
+    T.cos_tilt_max = cfg->cos_tilt_max;
+    T.alive_bonus = cfg->alive_bonus;
+    T.w_forward = cfg->w_forward;
+    T.w_action = cfg->w_action;
+    T.w_pose = cfg->w_pose;
+    T.joint_noise = cfg->joint_noise;
+    for (int k = 0; k < 7; ++k) T.home_base[k] = cfg->home_base[k];
+    for (int d = 0; d < n; ++d) T.home_q[d] = cfg->home_q[d];
+    // the contact slots of every link (FloatF::shape_body / shape_slot0 order:
+    // slot_body); the wave kernel's contact mask holds 32 slots
+    for (int j = 0; j < cfg->n_contact_links; ++j)
+        for (int slot = 0; slot < s->n_slots && slot < 32; ++slot)
+            if (s->slot_body[slot] == cfg->contact_links[j]) T.link_slots[j] |= 1u << slot;
+    e->task.n_obs = T.n_obs;  // mw_vecenv_obs_dim
+    MW_HIP(hipSetDevice(s->cfg.device));
+    // every dof in Force or Position mode; Position: the JointController runs
+    // every physics step (period = step size), as the Panda task sets it
+    const bool pos = cfg->action_mode == MW_FLOAT_ACTION_POSITION;
+    if ((rc = mw_set_joint_control_mode(s, 0, s->W, nullptr, 0, pos ? MW_MODE_POSITION : MW_MODE_FORCE))) return rc;
+    if (pos) s->period_ns = s->dt_ns;
+    // flush the modes, targets and gains now: from here on the command block
+    // is written on the device only, and a step must find nothing to stage
+    if ((rc = run_impl(s, 1, false))) return rc;
+    const size_t W = static_cast<size_t>(s->W);
+    MW_HIP(hipMalloc(&e->d_counters, 2 * W * sizeof(uint32_t)));
+    MW_HIP(hipMemsetAsync(e->d_counters, 0, 2 * W * sizeof(uint32_t), s->stream));
+    e->dev.episode = static_cast<uint32_t*>(e->d_counters);
+    e->dev.steps = e->dev.episode + W;
+    MW_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_asq), W * sizeof(float)));
+    MW_HIP(hipMemsetAsync(e->d_asq, 0, W * sizeof(float), s->stream));
+    s->env_owned = true;
+    *out = e.release();
+    return MW_OK;
+}
+
+static int floatenv_reset(mw_vecenv* e, float* obs) {
+    mw_sim* s = e->sim;
+    MW_HIP(mw::launch_float_env_post(s->d_params, e->ftask, s->dev, s->fdev, e->dev, e->d_asq, obs, nullptr, nullptr,
+                                     nullptr, s->n, s->W, 1, s->stream));
+    // a paused run applies the pending resets: the state (and the host
+    // getters) show the reset at once
+    return run_impl(s, 1, false);
+}
+
+static int floatenv_step(mw_vecenv* e, const void* a, float* o, float* r, uint8_t* d, float* to) {
+    mw_sim* s = e->sim;
+    const bool pos = e->ftask.action_mode == MW_FLOAT_ACTION_POSITION;
+    MW_HIP(mw::launch_float_env_action(static_cast<const float*>(a), pos ? s->dev.ptgt : s->dev.cmd, e->d_asq,
+                                       s->dev.div, s->dev.ndiv, s->n, s->W, s->stream));
+    if (pos) s->ptgt_stale = true;  // the host mirror of the targets re-reads the device copy
+    if (int rc = run_impl(s, 0, false)) return rc;
+    MW_HIP(mw::launch_float_env_post(s->d_params, e->ftask, s->dev, s->fdev, e->dev, e->d_asq, o, r, d, to, s->n,
+                                     s->W, 0, s->stream));
+    return MW_OK;
+}
+
 void mw_vecenv_destroy(mw_vecenv* e) {
     if (!e) return;
     if (e->sim && e->sim->stream) (void)hipStreamSynchronize(e->sim->stream);
+    if (e->floatenv && e->sim) e->sim->env_owned = false;
+    (void)hipFree(e->d_asq);
     (void)hipFree(e->d_counters);
     (void)hipFree(e->d_physics);
     (void)hipFree(e->d_lane);
@@ -2208,6 +2343,7 @@ int mw_vecenv_obs_dim(const mw_vecenv* e, int32_t* n) {
 
 int mw_vecenv_reset(mw_vecenv* e, float* obs) {
     if (!e || !obs) return fail(MW_EINVAL, "null argument");
+    if (e->floatenv) return floatenv_reset(e, obs);
     mw_sim* s = e->sim;
     MW_HIP(mw::launch_vecenv_reset(s->d_params, s->n, e->task, s->dev, e->dev, obs, s->W, s->stream));
     s->host_stale = true;
@@ -2216,6 +2352,10 @@ int mw_vecenv_reset(mw_vecenv* e, float* obs) {
 
 static int vec_common(mw_vecenv* e, int32_t T, const void* a, float* o, float* r, uint8_t* d, float* to) {
     if (!e || !a || !o || !r || !d || !to) return fail(MW_EINVAL, "null argument");
+    if (e->floatenv) {
+        if (T > 0) return fail(MW_EINVAL, "the fused rollout is not available for floating-base envs");
+        return floatenv_step(e, a, o, r, d, to);
+    }
     if (e->task.n_obs == 4 &&
         ((reinterpret_cast<uintptr_t>(o) | reinterpret_cast<uintptr_t>(to)) & 15u))
         return fail(MW_EINVAL, "obs buffers must be 16-byte aligned");

@@ -4,6 +4,7 @@ Layers:
   native   ctypes binding of the C ABI in include/mwstep.h (libmwstep.so)
   sim      Simulator: N worlds of one model, ScenarI/O-style accessors
   vecenv   VecEnv: device-resident batched gym tasks (torch tensors)
+  floatenv FloatVecEnv: the same for floating-base robots with contacts
   models   model files shipped with the build
 The ScenarI/O / gym_ignition mirrors live in the sibling packages
 ``scenario``, ``gym_ignition`` and ``gym_ignition_environments``.
@@ -31,4 +32,7 @@ def __getattr__(name):
     if name == "VecEnv":
         from .vecenv import VecEnv
         return VecEnv
+    if name == "FloatVecEnv":
+        from .floatenv import FloatVecEnv
+        return FloatVecEnv
     raise AttributeError(name)

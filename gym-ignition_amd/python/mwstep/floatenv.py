@@ -1,0 +1,250 @@
+"""Batched, device-resident environment for floating-base robots with contacts.
+
+``FloatVecEnv`` is the ``VecEnv`` of articulated models on a floating base (the
+quadruped, the iCub-class humanoid, any tree of up to 48 bodies that the
+world-per-wavefront kernel steps).  One ``step()`` is three launches on the
+current stream -- actions to device commands, the simulator's own run, and
+observation / reward / done / auto-reset -- with no host copy and no
+synchronisation, so a step can be captured into a graph.
+
+Observation, float32 ``[n_worlds, 13 + 2 n + n_contact_links]``: base position
+(3), orientation wxyz (4), world linear (3) and angular (3) velocity, joint
+positions and velocities, then per contact link the world z force (N) summed
+over its contact points.  Auto-reset follows the ``VecEnv`` convention: where
+``done`` is set, ``obs`` holds the first observation of the next episode and
+``info["terminal_obs"]`` the last one of the finished episode; the simulator
+itself takes the reset with the next step's run.
+
+While the env exists it owns the simulator's joint commands and pending
+resets: the host setters of ``env.sim`` that write them (``set("force_target"
+| "position_target" | "reset_q" | ...)``, ``reset_base_pose``,
+``set_control_mode``, ``set_pid``, ``set_state``) raise; the getters work.
+"""
+
+from __future__ import annotations
+
+import ctypes
+import math
+import os
+import xml.etree.ElementTree as ET
+from typing import Dict, Optional, Sequence, Tuple
+
+import numpy as np
+
+from . import native as N
+from .models import get_model_file
+from .sim import Simulator
+
+ACTION_MODES = {"torque": N.FLOAT_ACTION_TORQUE, "position": N.FLOAT_ACTION_POSITION}
+MAX_CONTACT_LINKS = 8
+
+
+def _torch():
+    import torch  # noqa: WPS433 (plumbing only: device memory + streams)
+    return torch
+
+
+def _fixed_parents(model: str) -> Dict[str, str]:
+    """child link -> parent link of every fixed joint of a URDF (file or text):
+    the model compiler lumps such a child into the body of its parent."""
+    try:
+        text = open(model).read() if os.path.exists(model) else model
+        root = ET.fromstring(text.strip())
+    except (OSError, ET.ParseError):
+        return {}
+    return {j.find("child").get("link"): j.find("parent").get("link")
+            for j in root.findall("joint") if j.get("type") == "fixed"}
+
+
+class FloatVecEnv:
+    """``n_worlds`` copies of one floating-base robot stepped together on one GPU."""
+
+    def __init__(self, model: str, n_worlds: int, action_mode: str = "position",
+                 home_q: Optional[Sequence[float]] = None,
+                 home_base: Sequence[float] = (0.0, 0.0, 1.0, 1.0, 0.0, 0.0, 0.0),
+                 pid_gains: Optional[Sequence[Sequence[float]]] = None,
+                 contact_links: Sequence = (), z_min: float = 0.0, max_tilt: float = math.pi,
+                 alive_bonus: float = 1.0, w_forward: float = 1.0, w_action: float = 0.0,
+                 w_pose: float = 0.0, joint_noise: float = 0.0, max_episode_steps: int = 1000,
+                 seed: int = 42, world_offset: int = 0, step_size: float = 1e-3, steps_per_run: int = 1,
+                 device: int = 0, pgs_iters: int = 20, ground_mu: float = 1.0):
+        """``model``: a shipped model's name or a URDF / SDF file.  ``home_q``
+        (one value per dof) and ``home_base`` (x y z qw qx qy qz) are the reset
+        state; ``pid_gains`` per dof ``(p, i, d)`` or the eight values of
+        ``Simulator.set_pid`` (position mode); either may be a function of the
+        joint names in dof order.  ``contact_links``: link names
+        or dof indices (-1 = the base) whose ground reaction enters the
+        observation.  ``max_tilt`` (rad): the episode ends when the base's z
+        axis leans further from the world's."""
+        torch = _torch()
+        if action_mode not in ACTION_MODES:
+            raise ValueError(f"unknown action_mode {action_mode!r}; known: {sorted(ACTION_MODES)}")
+        try:
+            model_file = get_model_file(model)
+        except ValueError:
+            model_file = model
+        self.action_mode = action_mode
+        self.n_worlds = n_worlds
+        self.device = torch.device("cuda", device)
+        self._h = None
+        with torch.cuda.device(self.device):
+            self._stream = torch.cuda.current_stream(self.device)
+            self.sim = Simulator(model_file, n_worlds=n_worlds, step_size=step_size,
+                                 steps_per_run=steps_per_run, device=device, pgs_iters=pgs_iters,
+                                 pose=tuple(home_base), stream=self._stream.cuda_stream)
+        sim = self.sim
+        n = sim.dofs
+        if home_q is None:
+            home_q = np.zeros(n)
+        if callable(home_q):      # of the joint names, in dof order
+            home_q = home_q(sim.joint_names)
+        if callable(pid_gains):
+            pid_gains = pid_gains(sim.joint_names)
+        self.home_q = np.ascontiguousarray(home_q, dtype=np.float32)
+        if self.home_q.shape != (n,):
+            raise ValueError(f"home_q must hold one value per dof ({n}), got shape {self.home_q.shape}")
+        self.home_base = np.ascontiguousarray(home_base, dtype=np.float32)
+        if self.home_base.shape != (7,):
+            raise ValueError("home_base must be (x, y, z, qw, qx, qy, qz)")
+        self.contact_links = self._resolve_links(model_file, contact_links)
+        sim.set_ground_plane(True, ground_mu)
+        sim.enable_contacts(True)
+        if pid_gains is not None:
+            if len(pid_gains) != n:
+                raise ValueError(f"pid_gains must hold one entry per dof ({n})")
+            big = float(np.finfo(np.float64).max)
+            for d, g in enumerate(pid_gains):
+                g = list(g)
+                sim.set_pid(d, g if len(g) == 8 else [g[0], g[1], g[2], -big, big, 0.0, -big, big])
+        links = np.ascontiguousarray(self.contact_links, dtype=np.int32)
+        cfg = N.MwFloatTaskConfig(
+            ACTION_MODES[action_mode], max_episode_steps, world_offset, len(links), seed & 0xFFFFFFFFFFFFFFFF,
+            z_min, math.cos(max_tilt), alive_bonus, w_forward, w_action, w_pose, joint_noise, 0.0,
+            (ctypes.c_float * 7)(*self.home_base.tolist()),
+            self.home_q.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+            links.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if len(links) else None)
+        h = ctypes.c_void_p()
+        N.check(N.lib().mw_floatenv_create(sim.handle, ctypes.byref(cfg), ctypes.byref(h)), "mw_floatenv_create")
+        self._h = h
+        no = ctypes.c_int32()
+        N.check(N.lib().mw_vecenv_obs_dim(h, ctypes.byref(no)))
+        self.obs_dim = no.value
+        self.action_dim = n
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.obs = torch.zeros((n_worlds, self.obs_dim), **f32)
+        self.reward = torch.zeros((n_worlds,), **f32)
+        self.done = torch.zeros((n_worlds,), dtype=torch.uint8, device=self.device)
+        self.terminal_obs = torch.zeros((n_worlds, self.obs_dim), **f32)
+
+    # ------------------------------------------------------------------
+    @classmethod
+    def icub(cls, n_worlds: int, **kw) -> "FloatVecEnv":
+        """The iCub-class humanoid (BASELINE config 5) from the reference
+        wrapper's pose and posture, under its posture-hold gains; the soles'
+        ground reaction in the observation."""
+        from .models import ICUB_POSE, icub_pid_gains, icub_posture
+
+        def gains(names):
+            return [[p, 0.0, d, -80.0, 80.0, 0.0, 0.0, -1.0] for p, d in icub_pid_gains(names)]
+        args = dict(action_mode="position", home_q=icub_posture, home_base=ICUB_POSE, pid_gains=gains,
+                    contact_links=("l_foot", "r_foot"), z_min=0.3, max_tilt=1.0, pgs_iters=50)
+        args.update(kw)
+        return cls("icub", n_worlds, **args)
+
+    @classmethod
+    def quadruped(cls, n_worlds: int, **kw) -> "FloatVecEnv":
+        """The 8-dof quadruped standing on its four feet (the shanks' spheres)."""
+        args = dict(action_mode="position", home_q=[0.6, -1.2] * 4, home_base=(0.0, 0.0, 0.45, 1.0, 0.0, 0.0, 0.0),
+                    pid_gains=[[400.0, 0.0, 10.0, -60.0, 60.0, 0.0, 0.0, -1.0]] * 8,
+                    contact_links=("shank_fl", "shank_fr", "shank_hl", "shank_hr"), z_min=0.15, max_tilt=1.0)
+        args.update(kw)
+        return cls("quadruped", n_worlds, **args)
+
+    # ------------------------------------------------------------------
+    def _resolve_links(self, model_file: str, links: Sequence):
+        """Link names / dof indices -> the dof index of the link's body (-1 =
+        the base); a link welded to its parent by fixed joints counts as the
+        body it is lumped into (the iCub's soles sit on the ankles' bodies)."""
+        if len(links) > MAX_CONTACT_LINKS:
+            raise ValueError(f"at most {MAX_CONTACT_LINKS} contact links")
+        known = {self.sim.base_frame: -1}
+        known.update({name: i for i, name in enumerate(self.sim.link_names)})
+        fixed = None
+        out = []
+        for link in links:
+            if isinstance(link, str):
+                name = link
+                while name not in known:
+                    if fixed is None:
+                        fixed = _fixed_parents(model_file)
+                    if name not in fixed:
+                        raise ValueError(f"link {link!r} not found in model {self.sim.model_name!r}")
+                    name = fixed[name]
+                out.append(known[name])
+            else:
+                out.append(int(link))
+        return out
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None:
+            N.lib().mw_vecenv_destroy(self._h)
+            self._h = None
+        if getattr(self, "sim", None) is not None:
+            self.sim.close()
+            self.sim = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check_actions(self, actions) -> None:
+        torch = _torch()
+        shape = (self.n_worlds, self.action_dim)
+        if not isinstance(actions, torch.Tensor) or actions.device != self.device:
+            raise TypeError(f"actions must be a torch tensor on {self.device}")
+        if actions.dtype != torch.float32 or tuple(actions.shape) != shape or not actions.is_contiguous():
+            raise TypeError(f"actions must be a contiguous {torch.float32} tensor of shape {shape}")
+
+    def reset(self):
+        """Reset every world (episode 0); returns obs [n_worlds, obs_dim].  The
+        simulator shows the reset state at once (a paused run applies it)."""
+        self.sim._cache.clear()
+        N.check(N.lib().mw_vecenv_reset(self._h, ctypes.c_void_p(self.obs.data_ptr())), "reset")
+        return self.obs
+
+    def step(self, actions) -> Tuple[object, object, object, Dict]:
+        """Asynchronous on the current stream; returns views of reused buffers."""
+        self._check_actions(actions)
+        self.sim._cache.clear()
+        N.check(N.lib().mw_vecenv_step(
+            self._h, ctypes.c_void_p(actions.data_ptr()), ctypes.c_void_p(self.obs.data_ptr()),
+            ctypes.c_void_p(self.reward.data_ptr()), ctypes.c_void_p(self.done.data_ptr()),
+            ctypes.c_void_p(self.terminal_obs.data_ptr())), "step")
+        return self.obs, self.reward, self.done, {"terminal_obs": self.terminal_obs}
+
+    def step_raw(self, actions_ptr: int) -> None:
+        """Launch one step with a raw device pointer (bench / graph capture)."""
+        N.check(N.lib().mw_vecenv_step(self._h, ctypes.c_void_p(actions_ptr),
+                                       ctypes.c_void_p(self.obs.data_ptr()),
+                                       ctypes.c_void_p(self.reward.data_ptr()),
+                                       ctypes.c_void_p(self.done.data_ptr()),
+                                       ctypes.c_void_p(self.terminal_obs.data_ptr())), "step")
+
+    def rollout(self, actions):
+        """Not available: a floating-base step is three launches, not a fused one."""
+        obs = self.obs
+        N.check(N.lib().mw_vecenv_rollout(
+            self._h, 1, ctypes.c_void_p(actions.data_ptr()), ctypes.c_void_p(obs.data_ptr()),
+            ctypes.c_void_p(self.reward.data_ptr()), ctypes.c_void_p(self.done.data_ptr()),
+            ctypes.c_void_p(self.terminal_obs.data_ptr())), "rollout")
+
+    def counters(self):
+        """(episode, steps) per world as int32 tensors (copies of the uint32 counters)."""
+        torch = _torch()
+        ep = torch.empty((self.n_worlds,), dtype=torch.int32, device=self.device)
+        st = torch.empty_like(ep)
+        N.check(N.lib().mw_vecenv_counters(self._h, ctypes.c_void_p(ep.data_ptr()),
+                                           ctypes.c_void_p(st.data_ptr())), "counters")
+        return ep, st

@@ -68,6 +68,32 @@ class MwTaskConfig(ctypes.Structure):
     ]
 
 
+FLOAT_ACTION_TORQUE = 0
+FLOAT_ACTION_POSITION = 1
+
+
+class MwFloatTaskConfig(ctypes.Structure):
+    """mw_float_task_config (include/mwstep.h)."""
+    _fields_ = [
+        ("action_mode", ctypes.c_int32),
+        ("max_episode_steps", ctypes.c_int32),
+        ("world_offset", ctypes.c_int32),
+        ("n_contact_links", ctypes.c_int32),
+        ("seed", ctypes.c_uint64),
+        ("z_min", ctypes.c_float),
+        ("cos_tilt_max", ctypes.c_float),
+        ("alive_bonus", ctypes.c_float),
+        ("w_forward", ctypes.c_float),
+        ("w_action", ctypes.c_float),
+        ("w_pose", ctypes.c_float),
+        ("joint_noise", ctypes.c_float),
+        ("pad_", ctypes.c_float),
+        ("home_base", ctypes.c_float * 7),
+        ("home_q", ctypes.POINTER(ctypes.c_float)),
+        ("contact_links", ctypes.POINTER(ctypes.c_int32)),
+    ]
+
+
 # (name, restype, argtypes) of every symbol in include/mwstep.h
 _P = ctypes.c_void_p
 _I = ctypes.c_int32
@@ -156,6 +182,7 @@ SIGNATURES = [
     ("mw_vecenv_rollout", ctypes.c_int, [_P, _I, _P, _P, _P, _P, _P]),
     ("mw_vecenv_counters", ctypes.c_int, [_P, _P, _P]),
     ("mw_vecenv_physics", ctypes.c_int, [_P, _P, _P]),
+    ("mw_floatenv_create", ctypes.c_int, [_P, ctypes.POINTER(MwFloatTaskConfig), ctypes.POINTER(_P)]),
 ]
 
 # include/mwscene.h

@@ -404,6 +404,68 @@ int mw_vecenv_counters(mw_vecenv* env, uint32_t* episode_dev, uint32_t* steps_de
  * env was created without randomisation. */
 int mw_vecenv_physics(mw_vecenv* env, float* mass_dev, float* gravity_z_dev);
 
+/* ---- batched environment of articulated floating-base models ----
+ * Any model stepped by the world-per-wavefront kernel with a floating base
+ * (mw_float_kernel == 2 and mw_is_floating: the quadruped, the iCub-class
+ * humanoid, any tree of <= 48 bodies without ball joints).  One step is three
+ * launches on the sim's stream -- actions -> device commands, the unchanged
+ * run, observation / reward / done / auto-reset -- with no host copy and no
+ * synchronisation, so a step can be captured into a graph.
+ *   actions  float32 [n_worlds, n_dofs]: joint torques (MW_FLOAT_ACTION_TORQUE,
+ *            every dof in Force mode, clipped to the effort limits by the run
+ *            as mw_set_joint_force_targets' values are) or Position-mode
+ *            targets (MW_FLOAT_ACTION_POSITION: JointController PID every
+ *            physics step, gains from mw_set_joint_pid before creation)
+ *   obs      float32 [n_worlds, 13 + 2 n_dofs + n_contact_links]: base position
+ *            (3), orientation wxyz (4), world linear velocity of the base
+ *            origin (3), world angular velocity (3) -- mw_get_base_velocity's
+ *            quantities --, q, qd, then per contact link the world z force (N)
+ *            summed over the link's contact points of the last physics step
+ *   done     base z < z_min, or the world z component of the base's z axis
+ *            < cos_tilt_max, or the world diverged (mw_diverged: its state is
+ *            not finite, or its action was not -- the env flags and counts
+ *            such a world itself, since the run's effort clamp would turn a
+ *            NaN torque into -effort silently), or max_episode_steps (0 =
+ *            none) reached
+ *   reward   alive_bonus [not done by height / tilt / divergence] + w_forward
+ *            v_x - w_action sum a^2 - w_pose sum (q - home_q)^2, on the state
+ *            after the run and before any reset
+ *   reset    q = clip(home_q + U(-joint_noise, joint_noise), limits) from
+ *            Philox4x32-10 keyed by seed, counter (world_offset + world,
+ *            episode, dof / 4, 0); qd = 0; base at home_base, at rest.  A done
+ *            world's reset is left on the device as pending resets, applied by
+ *            the next step's run exactly as the host reset setters' are (warm
+ *            start cold, PID state zero, divergence flag re-armed); its obs
+ *            row already shows the reset state (zero velocities and contact
+ *            forces), terminal_obs the finished episode's last observation.
+ * The handle is an mw_vecenv: mw_vecenv_destroy / _obs_dim / _reset / _step /
+ * _counters work on it (mw_vecenv_reset also runs the simulator paused, so the
+ * state getters show the reset at once); mw_vecenv_rollout fails with
+ * MW_EINVAL, mw_vecenv_physics with MW_ESTATE.
+ * While the env exists it owns the simulator's commands and pending resets:
+ * the host setters that write them -- mw_set_joint_{force,velocity,position}
+ * _targets, mw_reset_joint_positions / _velocities, mw_reset_base_pose /
+ * _velocity, mw_set_joint_control_mode, mw_set_joint_pid and mw_set_state --
+ * fail with MW_ESTATE instead of being overwritten by (or overwriting) the
+ * device writes; they work again after mw_vecenv_destroy. */
+#define MW_FLOAT_ACTION_TORQUE 0
+#define MW_FLOAT_ACTION_POSITION 1
+typedef struct {
+    int32_t action_mode;
+    int32_t max_episode_steps;      /* 0 = no time limit                    */
+    int32_t world_offset;           /* global index of world 0 (sharding)   */
+    int32_t n_contact_links;        /* <= 8                                 */
+    uint64_t seed;
+    float z_min, cos_tilt_max;
+    float alive_bonus, w_forward, w_action, w_pose;
+    float joint_noise;
+    float pad_;
+    float home_base[7];             /* x y z qw qx qy qz                    */
+    const float* home_q;            /* [n_dofs] (the caller's length; FloatVecEnv checks it) */
+    const int32_t* contact_links;   /* [n_contact_links] dof index of the link, -1 = base */
+} mw_float_task_config;
+int mw_floatenv_create(mw_sim* sim, const mw_float_task_config* cfg, mw_vecenv** out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,137 @@
+#!/usr/bin/env python3
+"""Overhead of the floating-base env's device layer (mwstep.FloatVecEnv).
+
+For the iCub at 512 worlds and the quadruped at 4,096 worlds, in one process:
+
+  env    a captured env.step: action kernel + the run + post kernel
+  bare   a captured sim.run_device(1) of an identically configured Simulator
+  floor  a captured chain of two one-element kernels (the cost of two more
+         graph nodes; torch has no empty kernel, `t.add_(1)` on one float is
+         the smallest it launches)
+
+each replayed --replays times per window between HIP events on the stream,
+the three graphs alternating over --rounds windows after a warm-up; the
+medians are reported.  The two env kernels move about W (obs_dim + n) 4 bytes
+(0.3 MB for the iCub case: far below a microsecond of HBM time), so launch
+cost is all they should add; the expectation checked here is
+
+  env - bare <= 1.25 x floor.
+
+Not a bench.py leg.  Prints one JSON line per model."""
+
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "gym-ignition_amd", "python"))
+
+
+def capture(torch, stream, fn, warm):
+    with torch.cuda.stream(stream):
+        for _ in range(warm):
+            fn()
+        stream.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=stream):
+            fn()
+        graph.replay()
+        stream.synchronize()
+    return graph
+
+
+def window(torch, stream, graph, replays):
+    """Microseconds per replay over one window of `replays` replays."""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    with torch.cuda.stream(stream):
+        e0.record(stream)
+        for _ in range(replays):
+            graph.replay()
+        e1.record(stream)
+        stream.synchronize()
+    return e0.elapsed_time(e1) * 1e3 / replays
+
+
+def bare_sim(torch, env, model, stream):
+    """A Simulator configured as the env's, holding the home posture."""
+    import numpy as np
+    from mwstep import get_model_file
+    from mwstep import native as N
+    from mwstep.sim import Simulator
+    W, s = env.n_worlds, env.sim
+    sim = Simulator(get_model_file(model), n_worlds=W, step_size=s.step_size, steps_per_run=s.steps_per_run,
+                    pgs_iters=env.pgs_iters, pose=tuple(env.home_base.tolist()), stream=stream.cuda_stream)
+    sim.set_ground_plane(True, 1.0)
+    sim.enable_contacts(True)
+    for d in range(sim.dofs):
+        sim.set_pid(d, s.pid(d))
+    sim.set("reset_q", np.tile(env.home_q.astype(np.float64), (W, 1)))
+    sim.run(paused=True)
+    sim.set_controller_period(s.step_size)
+    sim.set_control_mode(N.MODE_POSITION)
+    sim.set("position_target", np.tile(env.home_q.astype(np.float64), (W, 1)))
+    return sim
+
+
+def measure(torch, args, model, W):
+    import numpy as np
+    from mwstep import FloatVecEnv
+    stream = torch.cuda.Stream()
+    with torch.cuda.stream(stream):
+        env = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0)
+        env.pgs_iters = 50 if model == "icub" else 20
+        env.reset()
+        actions = torch.from_numpy(np.tile(env.home_q, (W, 1))).to(env.device)
+        sim = bare_sim(torch, env, model, stream)
+        one = torch.zeros(1, device=env.device)
+
+    def floor():
+        one.add_(1.0)
+        one.add_(1.0)
+
+    graphs = {"env": capture(torch, stream, lambda: env.step_raw(actions.data_ptr()), args.warmup),
+              "bare": capture(torch, stream, lambda: sim.run_device(1), args.warmup),
+              "floor": capture(torch, stream, floor, args.warmup)}
+    times = {k: [] for k in graphs}
+    for _ in range(args.rounds):
+        for k, g in graphs.items():
+            times[k].append(window(torch, stream, g, args.replays))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    done = int(env.counters()[0].sum().item())
+    z = env.sim.base_pose()[:, 2]
+    excess = med["env"] - med["bare"]
+    out = {"model": model, "n_worlds": W, "obs_dim": env.obs_dim, "action_dim": env.action_dim,
+           "replays_per_window": args.replays, "rounds": args.rounds,
+           "env_step_us": round(med["env"], 3), "bare_run_us": round(med["bare"], 3),
+           "two_node_floor_us": round(med["floor"], 3), "excess_us": round(excess, 3),
+           "excess_over_floor": round(excess / med["floor"], 3),
+           "within_floor_plus_25pct": bool(excess <= 1.25 * med["floor"]),
+           "spread_us": {k: [round(min(v), 3), round(max(v), 3)] for k, v in times.items()},
+           "bytes_moved_by_env_kernels": W * (env.obs_dim + env.action_dim) * 4,
+           "auto_resets_during_run": done, "base_z_range_after": [round(float(z.min()), 4), round(float(z.max()), 4)]}
+    env.close()
+    sim.close()
+    return out
+
+
+def main():
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--replays", type=int, default=2000, help="graph replays per timed window (>= 200)")
+    p.add_argument("--rounds", type=int, default=5, help="windows per graph, the three graphs alternating")
+    p.add_argument("--warmup", type=int, default=50, help="uncaptured calls before each capture")
+    p.add_argument("--icub-worlds", type=int, default=512)
+    p.add_argument("--quadruped-worlds", type=int, default=4096)
+    args = p.parse_args()
+    if args.replays < 200:
+        p.error("--replays must be >= 200")
+    import torch
+    if not torch.cuda.is_available():
+        sys.exit("bench_float_env.py needs the GPU: there is no CPU path to time")
+    for model, W in (("icub", args.icub_worlds), ("quadruped", args.quadruped_worlds)):
+        print(json.dumps(measure(torch, args, model, W)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
