@@ -7,10 +7,9 @@
 //                   (resets -> commands -> substeps -> readback, force command
 //                   consumed by the first substep), Physics.cpp:646-685,
 //                   :1330-1440, :2226-2345.
-//  vecenv_step    : one gym step of every world with the Task logic of
-//                   python/gym_ignition_environments/tasks/*.py fused in
-//                   (obs, reward, done, TimeLimit, auto-reset).
-//  vecenv_reset   : initial reset of every world (Philox4x32-10).
+//  vecenv_pid_step: one gym step of the position-target task (Panda).
+// The gym step / reset kernels of the CartPole and Pendulum tasks live in
+// vecenv_kernel.hip (built with kernarg preloading).
 #include <type_traits>
 
 #include "baked_models.hpp"
@@ -53,15 +52,12 @@ __device__ __forceinline__ bool base_nonfinite(const FreeState& b) {
 // folds the zeros / ones of its transforms, axes and inertias (CartPole
 // substep: 1507 -> 672 instructions).  The host selects a baked kernel only
 // when the loaded model's block is bit-identical (sim.cpp: baked_id).
-__constant__ constexpr baked::CartpoleBlock kCartpoleDev = {{MW_BAKED_CARTPOLE_INIT}};
-__constant__ constexpr baked::PendulumBlock kPendulumDev = {{MW_BAKED_PENDULUM_INIT}};
+// (The CartPole's and the Pendulum's blocks: vecenv_kernel.hip.)
 __constant__ constexpr baked::PandaBlock kPandaDev = {{MW_BAKED_PANDA_INIT}};
 
 template <int BAKED>
 __device__ __forceinline__ const ChainF* model_params(const ChainF* P) {
-    if constexpr (BAKED == baked::kCartpoleId) return reinterpret_cast<const ChainF*>(&kCartpoleDev);
-    else if constexpr (BAKED == baked::kPendulumId) return reinterpret_cast<const ChainF*>(&kPendulumDev);
-    else if constexpr (BAKED == baked::kPandaId) return reinterpret_cast<const ChainF*>(&kPandaDev);
+    if constexpr (BAKED == baked::kPandaId) return reinterpret_cast<const ChainF*>(&kPandaDev);
     else return P;
 }
 
@@ -100,134 +96,6 @@ __device__ __forceinline__ auto make_stage(BodyState* b, ImpulseFactor* f, SV7* 
     }
 }
 
-constexpr float kPi = 3.14159265358979323846f;
-
-// ----------------------------------------------------------- tasks ------
-// kinds: 0 CartPoleDiscreteBalancing, 1 CartPoleContinuousBalancing,
-//        2 CartPoleContinuousSwingup, 3 PendulumSwingUp
-template <int N, int KIND>
-__device__ __forceinline__ void task_reset(const TaskF& T, uint32_t w, uint32_t episode,
-                                           float (&q)[N], float (&qd)[N]) {
-    uint32_t r[4];
-    philox(T.seed_lo, T.seed_hi, w, episode, r);
-    if constexpr (KIND == 0 || KIND == 1) {
-        // x, dx, q, dq = U(-0.05, 0.05)   cartpole_discrete_balancing.py:137
-        q[0] = unif(r[0], -0.05f, 0.05f); qd[0] = unif(r[1], -0.05f, 0.05f);
-        q[1] = unif(r[2], -0.05f, 0.05f); qd[1] = unif(r[3], -0.05f, 0.05f);
-    } else if constexpr (KIND == 2) {
-        // q = pi - deg2rad(U(-60, 60)); x, dx, dq = U(-0.05, 0.05)  cartpole_continuous_swingup.py:145-146
-        q[1] = kPi - unif(r[0], -60.f, 60.f) * (kPi / 180.f);
-        q[0] = unif(r[1], -0.05f, 0.05f); qd[0] = unif(r[2], -0.05f, 0.05f);
-        qd[1] = unif(r[3], -0.05f, 0.05f);
-    } else {
-        // cos, sin, dq = observation_space.sample(); q = atan2(sin, cos)  pendulum_swingup.py:117-127
-        const float c = unif(r[0], -1.f, 1.f), s = unif(r[1], -1.f, 1.f);
-        q[0] = atan2f(s, c);
-        qd[0] = unif(r[2], -10.f, 10.f);
-    }
-}
-
-template <int N, int KIND>
-__device__ __forceinline__ void task_obs(const float (&q)[N], const float (&qd)[N], float (&o)[4]) {
-    if constexpr (KIND == 3) {
-        float s, c;
-        sincosf(q[0], &s, &c);
-        o[0] = c; o[1] = s; o[2] = qd[0]; o[3] = 0.f;
-    } else {
-        o[0] = q[0]; o[1] = qd[0]; o[2] = q[1]; o[3] = qd[1];   // [x, dx, q, dq]
-    }
-}
-
-template <int KIND>
-__device__ __forceinline__ bool task_done(const TaskF& T, const float (&o)[4]) {
-    constexpr int no = (KIND == 3) ? 3 : 4;
-    bool inside = true;
-#pragma unroll
-    for (int k = 0; k < no; ++k) inside = inside && (o[k] >= -T.hi[k]) && (o[k] <= T.hi[k]);
-    return !inside;
-}
-
-template <int N, int KIND>
-__device__ __forceinline__ float task_reward(const TaskF& T, const float (&q)[N], const float (&qd)[N],
-                                             const float (&o)[4], bool done) {
-    // no FMA contraction: the reward is bit-identical in the per-step and the
-    // fused-rollout kernels (contraction would otherwise depend on context)
-#pragma clang fp contract(off)
-    if constexpr (KIND == 0 || KIND == 1) {
-        float r = done ? 0.f : 1.f;
-        if (T.reward_cart_at_center)
-            r = r - 0.10f * fabsf(o[0]) - 0.10f * fabsf(o[1]) -
-                10.0f * (o[0] >= T.x_factor * 2.4f ? 1.f : 0.f);
-        return r;
-    } else if constexpr (KIND == 2) {
-        return (cosf(q[1]) + 1.f) * 0.5f - 0.1f * qd[0] * qd[0] -
-               10.0f * (q[0] >= T.x_factor * 2.4f ? 1.f : 0.f);
-    } else {
-        // the force target read after the run is the zero-filled JointForceCmd
-        // (Physics.cpp:2250-2254), so the 0.001 tau^2 term of
-        // pendulum_swingup.py:86-88 is identically zero
-        const float cost = (done ? 100.f : 0.f) + q[0] * q[0] + 0.1f * qd[0] * qd[0];
-        return -cost;
-    }
-}
-
-// Per-world physics sample of (world, episode): masses from Philox blocks
-// 1.., gravity from block 8 by Box-Muller (SDFRandomizer.sample,
-// randomizers/model/sdf.py:264-315: force_positive clips the SAMPLE at 0, so
-// an additive mass change is max(U(lo, hi), 0); cartpole.py:51-56 gravity).
-template <int N>
-__device__ __forceinline__ Dyn<N> sample_dyn(const ChainF* __restrict__ P, const TaskF& T, uint32_t w,
-                                             uint32_t episode, float& gz_out) {
-    Dyn<N> D = nominal_dyn<N>(P);
-    gz_out = 0.f;
-    if (T.randomize & kRandMass) {
-#pragma unroll
-        for (int b = 0; b < (N + 3) / 4; ++b) {
-            uint32_t r[4];
-            philox(T.seed_lo, T.seed_hi, w, episode, r, 1u + static_cast<uint32_t>(b));
-#pragma unroll
-            for (int k = 0; k < 4; ++k)
-                if (4 * b + k < N) D.m[4 * b + k] += fmaxf(unif(r[k], T.mass_lo, T.mass_hi), 0.f);
-        }
-    }
-    if (T.randomize & kRandGravity) {
-        uint32_t r[4];
-        philox(T.seed_lo, T.seed_hi, w, episode, r, 8u);
-        const float u1 = static_cast<float>((r[0] >> 8) + 1u) * (1.f / 16777216.f);  // (0, 1]
-        const float u2 = static_cast<float>(r[1] >> 8) * (1.f / 16777216.f);
-        const float z = sqrtf(-2.f * logf(u1)) * cosf(2.f * kPi * u2);
-        const float gz = T.g_mean + T.g_std * z;
-        D.g = {gz * T.gdir[0], gz * T.gdir[1], gz * T.gdir[2]};
-        gz_out = gz;
-    }
-    return D;
-}
-
-template <int N>
-__device__ __forceinline__ Dyn<N> load_dyn(const ChainF* __restrict__ P, const TaskF& T, const VecDev& V, int W,
-                                           int w) {
-    Dyn<N> D = nominal_dyn<N>(P);
-    if (T.randomize & kRandMass) {
-#pragma unroll
-        for (int d = 0; d < N; ++d) D.m[d] = V.rmass[d * W + w];
-    }
-    if (T.randomize & kRandGravity) {
-        const float gz = V.rgz[w];
-        D.g = {gz * T.gdir[0], gz * T.gdir[1], gz * T.gdir[2]};
-    }
-    return D;
-}
-
-template <int N>
-__device__ __forceinline__ void store_dyn(const TaskF& T, const VecDev& V, int W, int w, const Dyn<N>& D,
-                                          float gz) {
-    if (T.randomize & kRandMass) {
-#pragma unroll
-        for (int d = 0; d < N; ++d) V.rmass[d * W + w] = D.m[d];
-    }
-    if (T.randomize & kRandGravity) V.rgz[w] = gz;
-}
-
 template <int N>
 __device__ __forceinline__ void load_state(const SimDev& S, int W, int w, float (&q)[N], float (&qd)[N]) {
 #pragma unroll
@@ -244,16 +112,6 @@ __device__ __forceinline__ void store_state(const SimDev& S, int W, int w, const
     for (int d = 0; d < N; ++d) {
         S.q[d * W + w] = q[d];
         S.qd[d * W + w] = qd[d];
-    }
-}
-
-template <int NO>
-__device__ __forceinline__ void store_obs(float* __restrict__ dst, const float (&o)[4]) {
-    if constexpr (NO == 4) {
-        *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < NO; ++k) dst[k] = o[k];
     }
 }
 
@@ -357,98 +215,6 @@ __global__ void __launch_bounds__(256) scenario_run_kernel(const ChainF* __restr
 #pragma unroll
     for (int d = 0; d < N; ++d) bad = bad || nonfinite_bits(q[d]) || nonfinite_bits(qd[d]);
     if (bad) mark_diverged(S.div, S.ndiv, w);
-}
-
-template <int N, int KIND>
-__global__ void __launch_bounds__(256) vecenv_reset_kernel(const ChainF* __restrict__ P, TaskF T, SimDev S,
-                                                           VecDev V, float* __restrict__ obs, int W) {
-    const int w = blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= W) return;
-    float q[N], qd[N], o[4];
-    if (T.randomize) {
-        const uint32_t gw = T.world_offset + static_cast<uint32_t>(w);
-        float gz;
-        const Dyn<N> D = sample_dyn<N>(P, T, gw, 0u, gz);
-        store_dyn<N>(T, V, W, w, D, gz);
-    }
-    task_reset<N, KIND>(T, T.world_offset + static_cast<uint32_t>(w), 0u, q, qd);
-    task_obs<N, KIND>(q, qd, o);
-    constexpr int NO = (KIND == 3) ? 3 : 4;
-    store_obs<NO>(obs + static_cast<size_t>(w) * NO, o);
-    store_state<N>(S, W, w, q, qd);
-    V.episode[w] = 0u;
-    V.steps[w] = 0u;
-}
-
-// STEPS == 0: single step; otherwise loop over T_steps with [t, w] layouts.
-template <int N, int KIND, bool DUAL, bool CONS, bool ROLLOUT, int BAKED, bool RAND = false>
-__global__ void __launch_bounds__(256) vecenv_step_kernel(const ChainF* __restrict__ Pin, TaskF T, SimDev S,
-                                                          VecDev V, const void* __restrict__ actions,
-                                                          float* __restrict__ obs, float* __restrict__ reward,
-                                                          uint8_t* __restrict__ done_out,
-                                                          float* __restrict__ term_obs, int W, float dt,
-                                                          int substeps, int pgs_iters, int T_steps) {
-    const int w = blockIdx.x * blockDim.x + threadIdx.x;
-    if (w >= W) return;
-    const ChainF* __restrict__ P = model_params<BAKED>(Pin);
-    constexpr int NO = (KIND == 3) ? 3 : 4;
-    float q[N], qd[N];
-    load_state<N>(S, W, w, q, qd);
-    const uint32_t episode0 = V.episode[w];
-    uint32_t episode = episode0;
-    uint32_t steps = V.steps[w];
-    uint8_t act[N];
-    float vc[N];
-#pragma unroll
-    for (int d = 0; d < N; ++d) { act[d] = kActForce; vc[d] = 0.f; }
-    Dyn<N> D;
-    if constexpr (RAND) D = load_dyn<N>(P, T, V, W, w);
-    const int nsteps = ROLLOUT ? T_steps : 1;
-    for (int t = 0; t < nsteps; ++t) {
-        const size_t idx = static_cast<size_t>(t) * W + w;
-        float force;
-        if constexpr (KIND == 0) {
-            const int a = static_cast<const int32_t*>(actions)[idx];
-            force = (a == 1) ? T.force_mag : -T.force_mag;   // cartpole_discrete_balancing.py:70
-        } else {
-            force = static_cast<const float*>(actions)[idx];
-        }
-        // the driven joint ("linear" / "pivot") is dof 0; other joints are Idle
-        const float e = P->b[0].effort;
-        force = fminf(fmaxf(force, -e), e);
-        float tau[N], qdd[N];
-        for (int s = 0; s < substeps; ++s) {
-#pragma unroll
-            for (int d = 0; d < N; ++d) tau[d] = 0.f;
-            tau[0] = (s == 0) ? force : 0.f;
-            if constexpr (RAND) substep_dyn<N, DUAL, CONS>(P, q, qd, tau, act, vc, dt, pgs_iters, qdd, D);
-            else substep<N, DUAL, CONS>(P, q, qd, tau, act, vc, dt, pgs_iters, qdd);
-        }
-        float o[4];
-        task_obs<N, KIND>(q, qd, o);
-        const bool tdone = task_done<KIND>(T, o);
-        reward[idx] = task_reward<N, KIND>(T, q, qd, o, tdone);
-        steps += 1u;
-        const bool d_ = tdone || (T.max_steps > 0 && steps >= static_cast<uint32_t>(T.max_steps));
-        done_out[idx] = d_ ? 1 : 0;
-        if (d_) {
-            store_obs<NO>(term_obs + idx * NO, o);
-            episode += 1u;
-            steps = 0u;
-            if constexpr (RAND) {
-                // GazeboEnvRandomizer.reset: new physics and model sample per episode
-                float gz;
-                D = sample_dyn<N>(P, T, T.world_offset + static_cast<uint32_t>(w), episode, gz);
-                store_dyn<N>(T, V, W, w, D, gz);
-            }
-            task_reset<N, KIND>(T, T.world_offset + static_cast<uint32_t>(w), episode, q, qd);
-            task_obs<N, KIND>(q, qd, o);
-        }
-        store_obs<NO>(obs + idx * NO, o);
-    }
-    store_state<N>(S, W, w, q, qd);
-    if (episode != episode0) V.episode[w] = episode;  // changes only on auto-reset
-    V.steps[w] = steps;
 }
 
 // ------------------------------------------------- floating free body ----
@@ -930,38 +696,6 @@ hipError_t scenario_n(const ChainF* P, bool cons, bool dual, int baked, const Si
     return hipGetLastError();
 }
 
-template <int N, int KIND, bool ROLLOUT, bool RAND>
-hipError_t vec_nk(const ChainF* P, bool cons, bool dual, int baked, const TaskF& T, const SimDev& S,
-                  const VecDev& V, const void* a, float* o, float* r, uint8_t* d, float* to, int W,
-                  float dt, int substeps, int pgs, int Ts, hipStream_t st) {
-    const int B = block_for(W);
-    // constant-folded instantiations for the shipped models (their flags fix cons/dual)
-    if constexpr (N == 2 && KIND <= 2) {
-        if (baked == baked::kCartpoleId && cons && !dual) {
-            hipLaunchKernelGGL((dev::vecenv_step_kernel<N, KIND, false, true, ROLLOUT, baked::kCartpoleId, RAND>),
-                               grid_for(W, B), dim3(B), 0, st, P, T, S, V, a, o, r, d, to, W, dt, substeps, pgs, Ts);
-            return hipGetLastError();
-        }
-    }
-    if constexpr (N == 1 && KIND == 3) {
-        if (baked == baked::kPendulumId && !cons) {
-            hipLaunchKernelGGL((dev::vecenv_step_kernel<N, KIND, false, false, ROLLOUT, baked::kPendulumId, RAND>),
-                               grid_for(W, B), dim3(B), 0, st, P, T, S, V, a, o, r, d, to, W, dt, substeps, pgs, Ts);
-            return hipGetLastError();
-        }
-    }
-    if (!cons)
-        hipLaunchKernelGGL((dev::vecenv_step_kernel<N, KIND, false, false, ROLLOUT, 0, RAND>), grid_for(W, B), dim3(B),
-                           0, st, P, T, S, V, a, o, r, d, to, W, dt, substeps, pgs, Ts);
-    else if (!dual)
-        hipLaunchKernelGGL((dev::vecenv_step_kernel<N, KIND, false, true, ROLLOUT, 0, RAND>), grid_for(W, B), dim3(B),
-                           0, st, P, T, S, V, a, o, r, d, to, W, dt, substeps, pgs, Ts);
-    else
-        hipLaunchKernelGGL((dev::vecenv_step_kernel<N, KIND, true, true, ROLLOUT, 0, RAND>), grid_for(W, B), dim3(B),
-                           0, st, P, T, S, V, a, o, r, d, to, W, dt, substeps, pgs, Ts);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 int kernel_topology(const int* parents, int n) {
@@ -1098,21 +832,11 @@ hipError_t launch_free_run(const FreeF* F, const FreeDev& D, int W, const RunArg
     return hipGetLastError();
 }
 
-hipError_t launch_vecenv_reset(const ChainF* P, int n, const TaskF& T, const SimDev& S,
-                               const VecDev& V, float* obs, int W, hipStream_t st) {
+hipError_t launch_vecenv_pid_reset(const ChainF* P, int n, const TaskF& T, const SimDev& S, const VecDev& V,
+                                   float* obs, int W, hipStream_t st) {
+    if (n != 9) return hipErrorInvalidValue;
     const int B = block_for(W);
-    if (T.kind == 4 && n == 9)
-        hipLaunchKernelGGL((dev::vecenv_pid_reset_kernel<9>), grid_for(W, B), dim3(B), 0, st, P, T, S, V, obs, W);
-    else if (T.kind == 3 && n == 1)
-        hipLaunchKernelGGL((dev::vecenv_reset_kernel<1, 3>), grid_for(W, B), dim3(B), 0, st, P, T, S, V, obs, W);
-    else if (T.kind == 0 && n == 2)
-        hipLaunchKernelGGL((dev::vecenv_reset_kernel<2, 0>), grid_for(W, B), dim3(B), 0, st, P, T, S, V, obs, W);
-    else if (T.kind == 1 && n == 2)
-        hipLaunchKernelGGL((dev::vecenv_reset_kernel<2, 1>), grid_for(W, B), dim3(B), 0, st, P, T, S, V, obs, W);
-    else if (T.kind == 2 && n == 2)
-        hipLaunchKernelGGL((dev::vecenv_reset_kernel<2, 2>), grid_for(W, B), dim3(B), 0, st, P, T, S, V, obs, W);
-    else
-        return hipErrorInvalidValue;
+    hipLaunchKernelGGL((dev::vecenv_pid_reset_kernel<9>), grid_for(W, B), dim3(B), 0, st, P, T, S, V, obs, W);
     return hipGetLastError();
 }
 
@@ -1140,28 +864,6 @@ hipError_t launch_vecenv_pid_step(const ChainF* P, int n, int topo, bool cons, b
                            st, P, T, S, V, pid, targets, obs, reward, done, term_obs, W, dt, inv_dt, substeps,
                            pgs_iters);
     return hipGetLastError();
-}
-
-hipError_t launch_vecenv_step(const ChainF* P, int n, bool cons, bool dual, int baked, const TaskF& T,
-                              const SimDev& S, const VecDev& V, const void* actions, float* obs,
-                              float* reward, uint8_t* done, float* term_obs, int W, float dt,
-                              int substeps, int pgs_iters, int T_steps, hipStream_t st) {
-#define MW_VEC_R(NN, KK, RR)                                                                                 \
-    return (T_steps > 0)                                                                                     \
-               ? vec_nk<NN, KK, true, RR>(P, cons, dual, baked, T, S, V, actions, obs, reward, done, term_obs, W, \
-                                          dt, substeps, pgs_iters, T_steps, st)                              \
-               : vec_nk<NN, KK, false, RR>(P, cons, dual, baked, T, S, V, actions, obs, reward, done, term_obs,   \
-                                           W, dt, substeps, pgs_iters, 1, st)
-#define MW_VEC(NN, KK)              \
-    if (T.randomize) MW_VEC_R(NN, KK, true); \
-    MW_VEC_R(NN, KK, false)
-    if (T.kind == 3 && n == 1) { MW_VEC(1, 3); }
-    if (T.kind == 0 && n == 2) { MW_VEC(2, 0); }
-    if (T.kind == 1 && n == 2) { MW_VEC(2, 1); }
-    if (T.kind == 2 && n == 2) { MW_VEC(2, 2); }
-#undef MW_VEC
-#undef MW_VEC_R
-    return hipErrorInvalidValue;
 }
 
 }  // namespace mw

@@ -1,4 +1,5 @@
-// kernels.hpp -- host-callable launchers of the HIP kernels (kernels.hip).
+// kernels.hpp -- host-callable launchers of the HIP kernels (kernels.hip,
+// vecenv_kernel.hip, group_kernel.hip, float_env_kernel.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -132,8 +133,11 @@ constexpr int kWaveWarmWordsHost = 2 * (3 * 32 + 3 * kMaxBodies);
 // workspace words per world of a floating-tree model, -1 if n is not compiled in
 int float_workspace_words(int n, int n_slots);
 
+// vecenv_kernel.hip; a position-target task (kind 4) goes to launch_vecenv_pid_reset
 hipError_t launch_vecenv_reset(const ChainF* P, int n, const TaskF& T, const SimDev& S,
                                const VecDev& V, float* obs, int W, hipStream_t st);
+hipError_t launch_vecenv_pid_reset(const ChainF* P, int n, const TaskF& T, const SimDev& S, const VecDev& V,
+                                   float* obs, int W, hipStream_t st);
 
 // Position-target task (kind 4, Panda): actions float32 [W, n] are the
 // JointController position targets; PID every substep (period = step size).

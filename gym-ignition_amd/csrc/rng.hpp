@@ -1,5 +1,6 @@
 // rng.hpp -- Philox4x32-10 (Random123) and its uniform float mapping, shared
-// by the device tasks' resets and randomisation (kernels.hip, group_kernel.hip).
+// by the device tasks' resets and randomisation (vecenv_kernel.hip,
+// kernels.hip, group_kernel.hip).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -5,7 +5,7 @@ Behaviour follows the reference tasks
 cartpole_continuous_balancing.py, cartpole_continuous_swingup.py):
 observation [x, dx, q, dq], termination when the observation leaves the reset
 space, and the per-variant action, reward and reset distributions.  The same
-logic runs batched on the device in mwstep's VecEnv (kernels.hip).
+logic runs batched on the device in mwstep's VecEnv (vecenv_kernel.hip).
 """
 
 import abc

@@ -1,5 +1,6 @@
-"""Per-kernel VGPR / scratch / occupancy / LDS of kernels.hip (hipcc
--Rpass-analysis=kernel-resource-usage), as a table.  CPU only."""
+"""Per-kernel VGPR / scratch / occupancy / LDS of kernels.hip and
+vecenv_kernel.hip (hipcc -Rpass-analysis=kernel-resource-usage), as a table.
+CPU only."""
 import os
 import re
 import subprocess
@@ -8,10 +9,14 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 flags = ["-O3", "-std=c++17", "-fno-slp-vectorize", "-DMW_FAST_MATH", "-ffinite-math-only", "-fno-signed-zeros",
          *os.environ.get("EXTRA", "").split()]
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", *flags, f"-I{ROOT}/include",
-       f"-I{ROOT}/gym-ignition_amd/csrc", "-c", f"{ROOT}/gym-ignition_amd/csrc/kernels.hip",
-       "-o", "/tmp/_kr.o", "-Rpass-analysis=kernel-resource-usage"]
-out = subprocess.run(cmd, capture_output=True, text=True).stderr
+# source file -> its own flags (Makefile: VECENV_KFLAGS)
+SOURCES = {"kernels.hip": [], "vecenv_kernel.hip": ["-mllvm", "-amdgpu-kernarg-preload-count=16"]}
+out = ""
+for src, own in SOURCES.items():
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", *flags, *own, f"-I{ROOT}/include",
+           f"-I{ROOT}/gym-ignition_amd/csrc", "-c", f"{ROOT}/gym-ignition_amd/csrc/{src}",
+           "-o", "/tmp/_kr.o", "-Rpass-analysis=kernel-resource-usage"]
+    out += subprocess.run(cmd, capture_output=True, text=True).stderr
 rows, cur = [], {}
 for line in out.splitlines():
     m = re.search(r"Function Name: (\S+)", line)
