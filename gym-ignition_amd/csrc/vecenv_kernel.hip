@@ -123,9 +123,11 @@ __device__ __forceinline__ void task_obs(const float (&q)[N], const float (&qd)[
 template <int KIND, class TT>
 __device__ __forceinline__ bool task_done(const TT& T, const float (&o)[4]) {
     constexpr int no = (KIND == 3) ? 3 : 4;
+    // every comparison evaluated, combined bitwise: the same boolean as the
+    // short-circuit form without its nested exec-mask branches
     bool inside = true;
 #pragma unroll
-    for (int k = 0; k < no; ++k) inside = inside && (o[k] >= -T.hi[k]) && (o[k] <= T.hi[k]);
+    for (int k = 0; k < no; ++k) inside = inside & (o[k] >= -T.hi[k]) & (o[k] <= T.hi[k]);
     return !inside;
 }
 
@@ -253,16 +255,34 @@ __global__ void __launch_bounds__(256) vecenv_reset_kernel(const ChainF* __restr
 }
 
 // ROLLOUT: loop over A.T_steps with [t, w] layouts; otherwise a single step.
-// B: the workgroup size of the launch.  The 14 leading argument dwords are
+// B: the worlds of one workgroup.  The 14 leading argument dwords are
 // preloaded into SGPRs; A is fetched while the state loads are in flight.
-template <int N, int KIND, bool DUAL, bool CONS, bool ROLLOUT, int BAKED, bool RAND, int B>
+//
+// HELP: the workgroup has 2 * B threads (B == 64, two waves).  Wave 0 is the
+// kernel of worlds blockIdx.x * B + lane.  Wave 1, the helper, draws the same
+// worlds' next reset state (it depends on seed, world and episode only, not
+// on the physics) while wave 0 runs the physics, and leaves it in LDS; the
+// two meet at one workgroup barrier after wave 0 knows `done` and before its
+// first store, and a done lane reads its reset state from LDS instead of
+// running Philox behind the physics.  Every thread reaches the barrier: there
+// is no early return, lanes past W work on world W - 1 and store nothing.
+template <int N, int KIND, bool DUAL, bool CONS, bool ROLLOUT, int BAKED, bool RAND, int B, bool HELP = false>
 __global__ void __launch_bounds__(256) vecenv_step_kernel(float* __restrict__ sq, float* __restrict__ sqd,
                                                           uint32_t* __restrict__ ep, uint32_t* __restrict__ st,
                                                           const void* __restrict__ actions, int W, float dt,
                                                           int substeps, int pgs_iters,
                                                           VecArgs<RAND, BAKED == 0> A) {
-    const int w = blockIdx.x * B + threadIdx.x;
-    if (w >= W) return;
+    static_assert(!HELP || (B == 64 && !ROLLOUT && !RAND), "the helper wave serves the closed-loop 64-world blocks");
+    __shared__ float reset_lds[HELP ? 2 * N * B : 1];   // [component][lane]
+    const int lane = HELP ? static_cast<int>(threadIdx.x) & (B - 1) : static_cast<int>(threadIdx.x);
+    int w = blockIdx.x * B + lane;
+    bool live = true;
+    if constexpr (HELP) {
+        live = w < W;
+        w = live ? w : W - 1;
+    } else {
+        if (w >= W) return;
+    }
     constexpr int NO = (KIND == 3) ? 3 : 4;
     using ActT = std::conditional_t<KIND == 0, int32_t, float>;
     float q[N], qd[N];
@@ -290,6 +310,28 @@ __global__ void __launch_bounds__(256) vecenv_step_kernel(float* __restrict__ sq
     for (int d = 0; d < N; ++d) { act[d] = kActForce; vc[d] = 0.f; }
     Dyn<N> D;
     if constexpr (RAND) D = load_dyn<N>(P, A, A, W, w);
+    if constexpr (HELP) {
+        // the role is wave-uniform and chosen after the shared prologue
+        // (addresses, loads, A): the loads above still issue from the first
+        // instructions with no scalar wait in front of them
+        if (__builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x)) >= B) {
+            float rq[N], rqd[N];
+            task_reset<N, KIND>(A, A.world_offset + static_cast<uint32_t>(w), episode0 + 1u, rq, rqd);
+#pragma unroll
+            for (int d = 0; d < N; ++d) {
+                reset_lds[d * B + lane] = rq[d];
+                reset_lds[(N + d) * B + lane] = rqd[d];
+            }
+            __syncthreads();
+            // a use of the state loads on this side too: they stay in the
+            // shared prologue, ahead of the wait for A, instead of sinking
+            // into wave 0's branch.  Behind the barrier they landed long ago.
+#pragma unroll
+            for (int d = 0; d < N; ++d) asm volatile("" ::"v"(q[d]), "v"(qd[d]));
+            asm volatile("" ::"v"(steps), "v"(a0));
+            return;
+        }
+    }
     const int nsteps = ROLLOUT ? A.T_steps : 1;
     for (int t = 0; t < nsteps; ++t) {
         const size_t idx = static_cast<size_t>(t) * W + w;
@@ -312,12 +354,26 @@ __global__ void __launch_bounds__(256) vecenv_step_kernel(float* __restrict__ sq
             if constexpr (RAND) substep_dyn<N, DUAL, CONS>(P, q, qd, tau, act, vc, dt, pgs_iters, qdd, D);
             else substep<N, DUAL, CONS>(P, q, qd, tau, act, vc, dt, pgs_iters, qdd);
         }
+        // an unconditional use of the action: its load stays with the state
+        // loads above instead of sinking under the `substeps > 0` branch,
+        // behind the wait for A.  It stands ahead of the first store: after
+        // the stores it would make them wait for each other (the use needs a
+        // vmcnt wait, and by then the counter holds stores only).
+        if constexpr (!ROLLOUT) asm volatile("" ::"v"(a0));
         float o[4];
         task_obs<N, KIND>(q, qd, o);
         const bool tdone = task_done<KIND>(A, o);
-        reward[idx] = task_reward<N, KIND>(A, q, qd, o, tdone);
+        const float rew = task_reward<N, KIND>(A, q, qd, o, tdone);
+        if constexpr (!HELP) reward[idx] = rew;
         steps += 1u;
         const bool d_ = tdone || (A.max_steps > 0 && steps >= static_cast<uint32_t>(A.max_steps));
+        if constexpr (HELP) {
+            // the helper's reset state is in LDS behind this barrier; no
+            // store has been issued yet, so the barrier waits on LDS only
+            __syncthreads();
+            if (!live) return;
+            reward[idx] = rew;
+        }
         done_out[idx] = d_ ? 1 : 0;
         if (d_) {
             store_obs<NO>(term_obs + idx * NO, o);
@@ -329,15 +385,19 @@ __global__ void __launch_bounds__(256) vecenv_step_kernel(float* __restrict__ sq
                 D = sample_dyn<N>(P, A, A.world_offset + static_cast<uint32_t>(w), episode, gz);
                 store_dyn<N>(A, A, W, w, D, gz);
             }
-            task_reset<N, KIND>(A, A.world_offset + static_cast<uint32_t>(w), episode, q, qd);
+            if constexpr (HELP) {
+#pragma unroll
+                for (int d = 0; d < N; ++d) {
+                    q[d] = reset_lds[d * B + lane];
+                    qd[d] = reset_lds[(N + d) * B + lane];
+                }
+            } else {
+                task_reset<N, KIND>(A, A.world_offset + static_cast<uint32_t>(w), episode, q, qd);
+            }
             task_obs<N, KIND>(q, qd, o);
         }
         store_obs<NO>(obs + idx * NO, o);
     }
-    // an unconditional use of the action: its load stays with the state loads
-    // above instead of sinking under the `substeps > 0` branch, behind the
-    // wait for A
-    if constexpr (!ROLLOUT) asm volatile("" ::"v"(a0));
     store_state<N>(sq, sqd, W, w, q, qd);
     if (episode != episode0) ep[w] = episode;  // changes only on auto-reset
     st[w] = steps;
@@ -397,10 +457,15 @@ template <int N, int KIND, bool DUAL, bool CONS, bool ROLLOUT, int BAKED, bool R
 hipError_t vec_launch(const StepCall& c) {
     const auto A = step_args<RAND, BAKED == 0>(c);
     const int W = c.W;
+    // the closed-loop 64-world blocks run with a helper wave (the kernel's
+    // HELP); the rollout, the randomised physics (its sample_dyn stays
+    // inline) and the 256-thread path, where doubled waves would cost
+    // throughput, keep the inline reset
+    constexpr bool HELP = !ROLLOUT && !RAND;
     if (block_for(W) == 64)
-        hipLaunchKernelGGL((dev::vecenv_step_kernel<N, KIND, DUAL, CONS, ROLLOUT, BAKED, RAND, 64>), grid_for(W, 64),
-                           dim3(64), 0, c.st, c.S.q, c.S.qd, c.V.episode, c.V.steps, c.a, W, c.dt, c.substeps, c.pgs,
-                           A);
+        hipLaunchKernelGGL((dev::vecenv_step_kernel<N, KIND, DUAL, CONS, ROLLOUT, BAKED, RAND, 64, HELP>),
+                           grid_for(W, 64), dim3(HELP ? 128 : 64), 0, c.st, c.S.q, c.S.qd, c.V.episode, c.V.steps, c.a,
+                           W, c.dt, c.substeps, c.pgs, A);
     else
         hipLaunchKernelGGL((dev::vecenv_step_kernel<N, KIND, DUAL, CONS, ROLLOUT, BAKED, RAND, 256>), grid_for(W, 256),
                            dim3(256), 0, c.st, c.S.q, c.S.qd, c.V.episode, c.V.steps, c.a, W, c.dt, c.substeps, c.pgs,

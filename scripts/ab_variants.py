@@ -1,11 +1,12 @@
 """A/B timing of libmwstep build variants in ONE process (interleaved rounds).
 
-    python scripts/ab_variants.py lib1.so lib2.so ...
+    python scripts/ab_variants.py [--rounds=N] [--worlds=W] lib1.so lib2.so ...
 
 Per variant and round: (1) a fused 500-step rollout launch (HIP events on
 the launch stream): per-step compute of vecenv_step_kernel without launch
 gaps; (2) a hipGraph of 100 per-step launches: the closed-loop path of
-bench.py.  4096 CartPole worlds.  Prints the median over rounds."""
+bench.py.  4096 CartPole worlds unless --worlds=W.  Prints the median over
+the rounds (7 unless --rounds=N) and the closed-loop figure's min / max."""
 
 import ctypes
 import json
@@ -63,8 +64,10 @@ class Env:
 
 
 def main():
-    libs = sys.argv[1:]
-    W, T, G, rounds = 4096, 500, 100, 7
+    libs = [a for a in sys.argv[1:] if not a.startswith("--")]
+    opt = dict(a[2:].split("=") for a in sys.argv[1:] if a.startswith("--"))
+    rounds, W = int(opt.get("rounds", 7)), int(opt.get("worlds", 4096))
+    T, G = 500, 100
     stream = torch.cuda.Stream()
     acts = torch.randint(0, 2, (T, W), device="cuda", dtype=torch.int32)
     o = torch.empty((T, W, 4), device="cuda")
@@ -98,6 +101,9 @@ def main():
             res[p]["graph_us_per_step"].append(e1.elapsed_time(e2) * 1e3 / G)
     out = {os.path.basename(p): {k: round(statistics.median(v), 4) for k, v in d_.items()}
            for p, d_ in res.items()}
+    for p, d_ in res.items():   # the spread of the closed-loop figure over the rounds: the noise yardstick
+        g = d_["graph_us_per_step"]
+        out[os.path.basename(p)]["graph_us_per_step_min_max"] = [round(min(g), 4), round(max(g), 4)]
     print(json.dumps(out, indent=1))
 
 

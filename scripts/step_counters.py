@@ -25,7 +25,8 @@ def main():
             vals = {}
             for r in csv.DictReader(open(path)):
                 grid = r.get("Grid_Size") or r.get("Grid_Size_X")
-                if KERNEL in r["Kernel_Name"] and (not grid or int(grid) == 4096):
+                # 4096 worlds: 64 blocks of 64 threads, or of 128 with the helper wave
+                if KERNEL in r["Kernel_Name"] and (not grid or int(grid) in (4096, 8192)):
                     vals.setdefault(r["Counter_Name"], []).append(float(r["Counter_Value"]))
             for name, v in sorted(vals.items()):
                 out["counters"][name] = {"dispatches": len(v), "median": statistics.median(v),

@@ -13,6 +13,12 @@ library, disassembles that kernel with the ROCm LLVM tools and prints, as JSON:
   s_load                    scalar loads in the kernel body
   lgkm_waits_before_first_global_load
   s_load_after_first_vmcnt_wait
+  global_loads, global_loads_before_first_vmcnt_wait
+  vmcnt_waits_after_first_store   s_waitcnt vmcnt(..) that can execute after a
+                            global store (branch targets followed): a store
+                            waiting for the acknowledgement of earlier ones
+  lds_bytes                 group_segment_fixed_size of the kernel descriptor
+                            (> 0: the workgroup has a helper wave)
 
 With preloading, the compiler puts a 256-byte compatibility prologue in front
 of the body (it loads the preloaded arguments by hand, for firmware that does
@@ -32,7 +38,9 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT_LIB = os.path.join(ROOT, "gym-ignition_amd", "libmwstep.so")
-HEADLINE = re.compile(r"^_ZN2mw3dev18vecenv_step_kernelILi2ELi0ELb0ELb1ELb0ELi[1-9]\d*ELb0E(Li64E)?EEv\w*$")
+HEADLINE = re.compile(r"^_ZN2mw3dev18vecenv_step_kernelILi2ELi0ELb0ELb1ELb0ELi[1-9]\d*ELb0E(Li64E(Lb[01]E)?)?EEv\w*$")
+# every closed-loop (ROLLOUT == false) instantiation
+CLOSED_LOOP = re.compile(r"^_ZN2mw3dev18vecenv_step_kernelILi\d+ELi\d+ELb[01]ELb[01]ELb0E\w*$")
 BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
 
 
@@ -77,10 +85,13 @@ def elf_bytes_at(elf, addr, n):
     raise ValueError(f"address {addr:#x} is in no section")
 
 
-def analyse(lib_path):
+def analyse(lib_path, pattern=HEADLINE, every=False):
+    """The counts of the first kernel (sorted by name) whose symbol matches
+    `pattern`; with every=True a list, one entry per matching kernel."""
     tools = llvm_tools()
     if tools is None:
         return None
+    found = []
     readelf, objdump = tools
     with open(lib_path, "rb") as f:
         lib_bytes = f.read()
@@ -93,44 +104,74 @@ def analyse(lib_path):
             funcs, kds = {}, {}
             for line in syms.splitlines():
                 c = line.split()
-                if len(c) == 8 and c[3] == "FUNC" and HEADLINE.match(c[7]):
+                if len(c) == 8 and c[3] == "FUNC" and pattern.match(c[7]):
                     funcs[c[7]] = int(c[1], 16)
                 elif len(c) == 8 and c[3] == "OBJECT" and c[7].endswith(".kd"):
                     kds[c[7][:-3]] = int(c[1], 16)
             if not funcs:
                 continue
-            name = sorted(funcs)[0]
-            kd = elf_bytes_at(elf, kds[name], 64)   # amd_kernel_code descriptor, 64 bytes
-            kernarg_size, = struct.unpack_from("<I", kd, 8)
-            preload, = struct.unpack_from("<H", kd, 58)
-            preload &= 0x7F
-            dis = subprocess.run([objdump, "-d", f"--disassemble-symbols={name}", path], capture_output=True,
-                                 text=True, check=True).stdout
-            insts = []
-            for line in dis.splitlines():
-                m = re.match(r"^\s+(\S+)\s*(.*?)\s*// ([0-9A-Fa-f]+):", line)
-                if m:
-                    insts.append((int(m.group(3), 16), m.group(1), m.group(2)))
-            body_at = funcs[name] + (256 if preload else 0)
-            body = [(op, args) for a, op, args in insts if a >= body_at]
-            prologue = [(op, args) for a, op, args in insts if a < body_at]
-            ops = [op for op, _ in body]
-            first_gl = next((k for k, op in enumerate(ops) if op.startswith("global_load")), len(ops))
-            first_vm = next((k for k, (op, args) in enumerate(body) if op == "s_waitcnt" and "vmcnt" in args),
-                            len(ops))
-            return {
-                "library": os.path.basename(lib_path),
-                "kernel": name,
-                "kernarg_size": kernarg_size,
-                "kernarg_preload_dwords": preload,
-                "instructions": len(body),
-                "s_load": sum(op.startswith("s_load") for op in ops),
-                "prologue_s_load": sum(op.startswith("s_load") for op, _ in prologue),
-                "lgkm_waits_before_first_global_load": sum(
-                    op == "s_waitcnt" and "lgkmcnt" in args for op, args in body[:first_gl]),
-                "s_load_after_first_vmcnt_wait": sum(op.startswith("s_load") for op in ops[first_vm:]),
-            }
-    return {}
+            for name in sorted(funcs):
+                found.append(_counts(lib_path, elf, path, objdump, name, funcs[name], kds[name]))
+                if not every:
+                    return found[0]
+    return found if every else {}
+
+
+def _counts(lib_path, elf, path, objdump, name, func_at, kd_at):
+    kd = elf_bytes_at(elf, kd_at, 64)   # amd_kernel_code descriptor, 64 bytes
+    lds_bytes, = struct.unpack_from("<I", kd, 0)   # group_segment_fixed_size
+    kernarg_size, = struct.unpack_from("<I", kd, 8)
+    preload, = struct.unpack_from("<H", kd, 58)
+    preload &= 0x7F
+    dis = subprocess.run([objdump, "-d", f"--disassemble-symbols={name}", path], capture_output=True,
+                         text=True, check=True).stdout
+    insts = []
+    for line in dis.splitlines():
+        m = re.match(r"^\s+(\S+)\s*(.*?)\s*// ([0-9A-Fa-f]+):", line)
+        if m:
+            insts.append((int(m.group(3), 16), m.group(1), m.group(2)))
+    body_at = func_at + (256 if preload else 0)
+    body = [(op, args) for a, op, args in insts if a >= body_at]
+    prologue = [(op, args) for a, op, args in insts if a < body_at]
+    ops = [op for op, _ in body]
+    vm_wait = [op == "s_waitcnt" and "vmcnt" in args for op, args in body]
+    first_gl = next((k for k, op in enumerate(ops) if op.startswith("global_load")), len(ops))
+    first_vm = next((k for k, v in enumerate(vm_wait) if v), len(ops))
+    # vector-memory waits that can EXECUTE after a global store: reachability
+    # over the branch targets, not position in the listing (the helper wave's
+    # code lies behind wave 0's stores in the file and never runs after them)
+    addr = [a for a, _, _ in insts if a >= body_at]
+    at = {a: k for k, a in enumerate(addr)}
+    succ = []
+    for k, (op, args) in enumerate(body):
+        nxt = [] if op in ("s_endpgm", "s_branch") or k + 1 == len(body) else [k + 1]
+        if op == "s_branch" or op.startswith("s_cbranch"):
+            imm = int(args.split()[-1], 0) & 0xFFFF
+            nxt.append(at[addr[k] + 4 + 4 * (imm - 0x10000 if imm & 0x8000 else imm)])
+        succ.append(nxt)
+    todo = [n for k, op in enumerate(ops) if op.startswith("global_store") for n in succ[k]]
+    after_store = set()
+    while todo:
+        k = todo.pop()
+        if k not in after_store:
+            after_store.add(k)
+            todo.extend(succ[k])
+    return {
+        "library": os.path.basename(lib_path),
+        "kernel": name,
+        "kernarg_size": kernarg_size,
+        "kernarg_preload_dwords": preload,
+        "lds_bytes": lds_bytes,
+        "instructions": len(body),
+        "s_load": sum(op.startswith("s_load") for op in ops),
+        "prologue_s_load": sum(op.startswith("s_load") for op, _ in prologue),
+        "lgkm_waits_before_first_global_load": sum(
+            op == "s_waitcnt" and "lgkmcnt" in args for op, args in body[:first_gl]),
+        "s_load_after_first_vmcnt_wait": sum(op.startswith("s_load") for op in ops[first_vm:]),
+        "global_loads_before_first_vmcnt_wait": sum(op.startswith("global_load") for op in ops[:first_vm]),
+        "global_loads": sum(op.startswith("global_load") for op in ops),
+        "vmcnt_waits_after_first_store": sum(vm_wait[k] for k in after_store),
+    }
 
 
 def main():
