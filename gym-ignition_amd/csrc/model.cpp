@@ -948,4 +948,21 @@ ChainModel compile_urdf(const std::string& path_or_xml, const double pose[7]) {
     throw std::runtime_error("expected a URDF <robot> or an SDF <sdf> model (got <" + root->tag + ">)");
 }
 
+void quat_of(const std::array<double, 9>& R, double q[4]) {
+    const double tr = R[0] + R[4] + R[8];
+    if (tr > 0) {
+        const double k = 0.5 / std::sqrt(tr + 1.0);
+        q[0] = 0.25 / k; q[1] = (R[7] - R[5]) * k; q[2] = (R[2] - R[6]) * k; q[3] = (R[3] - R[1]) * k;
+    } else if (R[0] > R[4] && R[0] > R[8]) {
+        const double k = 2.0 * std::sqrt(1.0 + R[0] - R[4] - R[8]);
+        q[0] = (R[7] - R[5]) / k; q[1] = 0.25 * k; q[2] = (R[1] + R[3]) / k; q[3] = (R[2] + R[6]) / k;
+    } else if (R[4] > R[8]) {
+        const double k = 2.0 * std::sqrt(1.0 + R[4] - R[0] - R[8]);
+        q[0] = (R[2] - R[6]) / k; q[1] = (R[1] + R[3]) / k; q[2] = 0.25 * k; q[3] = (R[5] + R[7]) / k;
+    } else {
+        const double k = 2.0 * std::sqrt(1.0 + R[8] - R[0] - R[4]);
+        q[0] = (R[3] - R[1]) / k; q[1] = (R[2] + R[6]) / k; q[2] = (R[5] + R[7]) / k; q[3] = 0.25 * k;
+    }
+}
+
 }  // namespace mw

@@ -14,6 +14,7 @@
 #pragma once
 
 #include <array>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -89,5 +90,18 @@ struct ChainModel {
 // (World::insertModel, World.cpp:169-177).
 // Throws std::runtime_error with a message on unsupported / malformed input.
 ChainModel compile_urdf(const std::string& path_or_xml, const double pose[7]);
+
+// quaternion wxyz of a row-major rotation
+void quat_of(const std::array<double, 9>& R, double q[4]);
+
+// float32 of a host double; "unlimited" is FLT_MAX on the device (finite-math-only kernels)
+inline float to_f32(double v) {
+    const double big = static_cast<double>(std::numeric_limits<float>::max());
+    return static_cast<float>(v > big ? big : (v < -big ? -big : v));
+}
+
+// a joint's default gains, ignition::math::PID(1, 0.1, 0.01, -1, 0, -1, 0, 0) (Joint.cpp:63), as
+// {p, i, d, cmdMin, cmdMax, cmdOffset, iMin, iMax}
+constexpr std::array<double, 8> kDefaultPid = {1.0, 0.1, 0.01, 0.0, -1.0, 0.0, 0.0, -1.0};
 
 }  // namespace mw

@@ -22,10 +22,16 @@
 #include <string>
 #include <vector>
 
+#include "device_mem.hpp"
 #include "errors.hpp"
 #include "hull.hpp"
 #include "model.hpp"
 #include "scene_params.hpp"
+
+using mw::copy_str;
+using mw::fail;
+using mw::kDefaultPid;
+using mw::to_f32;
 
 namespace mw {
 hipError_t launch_scene_run(const SceneF* P, int nv, const SceneDev& D, const PidF* pid, const SceneGates& G, int W,
@@ -55,30 +61,11 @@ void fill_hull(mw::ScHull& H, const mw::HostHull& h) {
         }
 }
 
-int fail(int code, const std::string& msg) {
-    mw::set_last_error(msg);
-    return code;
-}
-
-#define SC_HIP(call)                                                                      \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess)                                                             \
-            return fail(MW_EHIP, std::string(#call " failed: ") + hipGetErrorString(e_)); \
-    } while (0)
-
 constexpr int NBMAX = mw::kScMaxBodies;
 constexpr int KMAX = mw::kScMaxModels;
 constexpr int NNMAX = mw::kScMaxNodes;
 constexpr int CMAX = mw::kScMaxContacts;
 constexpr int SLOTS = mw::kScWrenchSlots;
-// ignition::math::PID(1, 0.1, 0.01, -1, 0, -1, 0, 0) (Joint.cpp:63)
-constexpr std::array<double, 8> kDefaultPid = {1.0, 0.1, 0.01, 0.0, -1.0, 0.0, 0.0, -1.0};
-
-float to_f32(double v) {
-    const double big = static_cast<double>(std::numeric_limits<float>::max());
-    return static_cast<float>(v > big ? big : (v < -big ? -big : v));
-}
 
 struct SceneModel {
     mw::ChainModel m;
@@ -96,8 +83,10 @@ struct SceneModel {
 struct mw_scene {
     mw_config cfg{};
     int W = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    // declared before every buffer: members are destroyed in reverse order, so
+    // a stream created here outlives the buffers and is destroyed last
+    mw::stream_ptr own_stream;
+    hipStream_t stream = nullptr;  // own_stream or the caller's (mw_scene_set_stream)
     std::vector<SceneModel> models;
     int NB = 0;                    // bodies (= dofs)
     int nv = 0;
@@ -106,36 +95,36 @@ struct mw_scene {
     double mu = 1.0;
     int64_t iterations = 0, dt_ns = 0;
     mw::SceneF hp{};
-    mw::SceneF* dp = nullptr;
+    mw::dev_ptr<mw::SceneF> dp;
     mw::SceneDev dev{};
     // device blocks
-    void* d_joint = nullptr;       // [q qd qdd | cmd vtgt rq rqd ptgt | act rflag | pid_e pid_i pid_u]
-    void* d_base = nullptr;        // [base 13K | rpose 7K | rvel 6K][W] f32 + bflag [K][W]
-    void* d_misc = nullptr;        // present [W] | ncontact [W] | overflow | wlast [S][NN][W]
-    float* d_wrench = nullptr;     // [S][6][NN][W]
-    float* d_contact = nullptr;    // [contact_cap][12][W]
+    mw::dev_ptr<void> d_joint;     // [q qd qdd | cmd vtgt rq rqd ptgt | act rflag | pid_e pid_i pid_u]
+    mw::dev_ptr<void> d_base;      // [base 13K | rpose 7K | rvel 6K][W] f32 + bflag [K][W]
+    mw::dev_ptr<void> d_misc;      // present [W] | ncontact [W] | overflow | wlast [S][NN][W]
+    mw::dev_ptr<float[]> d_wrench;   // [S][6][NN][W]
+    mw::dev_ptr<float[]> d_contact;  // [contact_cap][12][W]
     int contact_cap = CMAX;        // contact points per world of the contact output
-    float* d_big = nullptr;        // large-contact workspace (SceneDev::big), big_bytes long
+    mw::dev_ptr<float[]> d_big;    // large-contact workspace (SceneDev::big), big_bytes long
     size_t big_bytes = 0;
-    float* d_wphys = nullptr;      // [4][W]: gravity xyz, ground friction per world
-    int32_t* d_warm = nullptr;     // [kScWarmWords][W]: exact-LCP warm-start record (SceneDev::warm)
-    mw::PidF* d_pid = nullptr;
+    mw::dev_ptr<float[]> d_wphys;  // [4][W]: gravity xyz, ground friction per world
+    mw::dev_ptr<int32_t[]> d_warm; // [kScWarmWords][W]: exact-LCP warm-start record (SceneDev::warm)
+    mw::dev_ptr<mw::PidF[]> d_pid;
     // pinned host mirrors with the device layouts
-    uint8_t* h_joint = nullptr;
-    uint8_t* h_base = nullptr;
-    uint32_t* h_present = nullptr;
-    int32_t* h_wlast = nullptr;
-    float* h_wrench = nullptr;
-    float* h_contact = nullptr;
-    int32_t* h_ncontact = nullptr;
-    int32_t* h_overflow = nullptr;  // pinned copy of the device drop counter
-    uint64_t* h_ndiv = nullptr;     // pinned copy of the count of worlds flagged diverged
+    mw::pin_ptr<uint8_t[]> h_joint;
+    mw::pin_ptr<uint8_t[]> h_base;
+    mw::pin_ptr<uint32_t[]> h_present;
+    mw::pin_ptr<int32_t[]> h_wlast;
+    mw::pin_ptr<float[]> h_wrench;
+    mw::pin_ptr<float[]> h_contact;
+    mw::pin_ptr<int32_t[]> h_ncontact;
+    mw::pin_ptr<int32_t> h_overflow;  // pinned copy of the device drop counter
+    mw::pin_ptr<uint64_t> h_ndiv;     // pinned copy of the count of worlds flagged diverged
     int64_t div_seen = 0;           // flagged worlds already reported
-    float* h_wphys = nullptr;       // pinned mirror of d_wphys (uploaded with the presence words)
+    mw::pin_ptr<float[]> h_wphys;     // pinned mirror of d_wphys (uploaded with the presence words)
     int64_t overflow_seen = 0;      // drops already reported
     int32_t lcp_mode = MW_LCP_EXACT;  // mw_scene_set_lcp_solver
     int32_t lcp_solves = 48;        // linear solves per world-step (scene leg: 24 -> 724 unconverged, 48 -> 0; profiles/r05t)
-    mw::PidF* h_pid = nullptr;
+    mw::pin_ptr<mw::PidF[]> h_pid;
     size_t jrows = 0;              // NBMAX * W
     // host-only component data
     std::vector<int32_t> mode;     // [dof][W]
@@ -155,7 +144,7 @@ struct mw_scene {
     bool dev_cmd_stale = false;
 
     size_t jidx(int d, int w) const { return static_cast<size_t>(d) * W + w; }
-    float* hq() { return reinterpret_cast<float*>(h_joint); }
+    float* hq() { return reinterpret_cast<float*>(h_joint.get()); }
     float* hqd() { return hq() + jrows; }
     float* hqdd() { return hq() + 2 * jrows; }
     float* hcmd() { return hq() + 3 * jrows; }
@@ -163,26 +152,34 @@ struct mw_scene {
     float* hrq() { return hq() + 5 * jrows; }
     float* hrqd() { return hq() + 6 * jrows; }
     float* hptgt() { return hq() + 7 * jrows; }
-    uint8_t* hact() { return h_joint + 8 * jrows * sizeof(float); }
+    uint8_t* hact() { return h_joint.get() + 8 * jrows * sizeof(float); }
     uint8_t* hrflag() { return hact() + jrows; }
     size_t state_bytes() const { return 3 * jrows * sizeof(float); }
     size_t cmd_off() const { return state_bytes(); }
     size_t cmd_bytes() const { return 5 * jrows * sizeof(float) + 2 * jrows; }
     size_t joint_bytes() const { return cmd_off() + cmd_bytes() + 3 * jrows * sizeof(float); }
     size_t krows() const { return static_cast<size_t>(KMAX) * W; }
-    float* hbase(int m, int f, int w) { return reinterpret_cast<float*>(h_base) + (static_cast<size_t>(13 * m + f)) * W + w; }
+    float* hbase(int m, int f, int w) {
+        return reinterpret_cast<float*>(h_base.get()) + (static_cast<size_t>(13 * m + f)) * W + w;
+    }
     float* hrpose(int m, int f, int w) {
-        return reinterpret_cast<float*>(h_base) + 13 * krows() + static_cast<size_t>(7 * m + f) * W + w;
+        return reinterpret_cast<float*>(h_base.get()) + 13 * krows() + static_cast<size_t>(7 * m + f) * W + w;
     }
     float* hrvel(int m, int f, int w) {
-        return reinterpret_cast<float*>(h_base) + 20 * krows() + static_cast<size_t>(6 * m + f) * W + w;
+        return reinterpret_cast<float*>(h_base.get()) + 20 * krows() + static_cast<size_t>(6 * m + f) * W + w;
     }
-    uint8_t* hbflag() { return h_base + 26 * krows() * sizeof(float); }
+    uint8_t* hbflag() { return h_base.get() + 26 * krows() * sizeof(float); }
     size_t base_bytes() const { return 26 * krows() * sizeof(float) + krows(); }
     int model_of_dof(int d) const {
         for (size_t m = 0; m < models.size(); ++m)
             if (d >= models[m].body0 && d < models[m].body0 + models[m].m.dofs()) return static_cast<int>(m);
         return -1;
+    }
+
+    // what mw_scene_destroy does before the members release their resources
+    ~mw_scene() {
+        (void)hipSetDevice(cfg.device);
+        if (stream) (void)hipStreamSynchronize(stream);
     }
 };
 
@@ -386,7 +383,7 @@ void build_params(mw_scene* s) {
 }
 
 int sync(mw_scene* s) {
-    SC_HIP(hipStreamSynchronize(s->stream));
+    MW_HIP(hipStreamSynchronize(s->stream));
     s->idle = true;
     return MW_OK;
 }
@@ -415,7 +412,7 @@ int flush(mw_scene* s, bool defer, bool direct = false) {
                      s->pid_dirty || (s->dev_cmd_stale && !direct);
     if (!any) return MW_OK;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    SC_HIP(hipStreamIsCapturing(s->stream, &cap));
+    MW_HIP(hipStreamIsCapturing(s->stream, &cap));
     if (cap != hipStreamCaptureStatusNone)
         return fail(MW_ESTATE, "pending commands, resets or model changes cannot be captured into a graph: "
                                "apply them with a run before capturing");
@@ -425,9 +422,9 @@ int flush(mw_scene* s, bool defer, bool direct = false) {
         if (int rc = sync(s)) return rc;
     if (s->params_dirty) {
         if (int rc = ensure_big(s)) return rc;
-        SC_HIP(hipMemcpyAsync(s->dp, &s->hp, sizeof(mw::SceneF), hipMemcpyHostToDevice, s->stream));
+        MW_HIP(hipMemcpyAsync(s->dp.get(), &s->hp, sizeof(mw::SceneF), hipMemcpyHostToDevice, s->stream));
         // new slots / pairs: the warm-start keys of the old layout mean nothing
-        SC_HIP(hipMemsetAsync(s->d_warm, 0, s->W * sizeof(int32_t), s->stream));
+        MW_HIP(hipMemsetAsync(s->d_warm.get(), 0, s->W * sizeof(int32_t), s->stream));
         s->params_dirty = false;
     }
     if (direct) {
@@ -437,26 +434,28 @@ int flush(mw_scene* s, bool defer, bool direct = false) {
             s->dev_cmd_stale = true;
         }
     } else if (s->cmd_dirty || s->dev_cmd_stale) {
-        SC_HIP(hipMemcpyAsync(static_cast<uint8_t*>(s->d_joint) + s->cmd_off(), s->h_joint + s->cmd_off(),
+        MW_HIP(hipMemcpyAsync(static_cast<uint8_t*>(s->d_joint.get()) + s->cmd_off(), s->h_joint.get() + s->cmd_off(),
                               s->cmd_bytes(), hipMemcpyHostToDevice, s->stream));
         s->clear_cmd = s->clear_cmd || s->cmd_dirty;
         s->dev_cmd_stale = false;
     }
     if (s->base_dirty) {
         const size_t off = 13 * s->krows() * sizeof(float);
-        SC_HIP(hipMemcpyAsync(static_cast<uint8_t*>(s->d_base) + off, s->h_base + off, s->base_bytes() - off,
-                              hipMemcpyHostToDevice, s->stream));
+        MW_HIP(hipMemcpyAsync(static_cast<uint8_t*>(s->d_base.get()) + off, s->h_base.get() + off,
+                              s->base_bytes() - off, hipMemcpyHostToDevice, s->stream));
         s->clear_base = true;
     }
     if (s->present_dirty) {
-        SC_HIP(hipMemcpyAsync(s->dev.present, s->h_present, s->W * sizeof(uint32_t), hipMemcpyHostToDevice,
+        MW_HIP(hipMemcpyAsync(s->dev.present, s->h_present.get(), s->W * sizeof(uint32_t), hipMemcpyHostToDevice,
                               s->stream));
-        SC_HIP(hipMemcpyAsync(s->d_wphys, s->h_wphys, 4 * s->W * sizeof(float), hipMemcpyHostToDevice, s->stream));
+        MW_HIP(hipMemcpyAsync(s->d_wphys.get(), s->h_wphys.get(), 4 * s->W * sizeof(float), hipMemcpyHostToDevice,
+                              s->stream));
     }
     if (s->wrench_dirty) {
         const size_t nn = static_cast<size_t>(SLOTS) * NNMAX * s->W;
-        SC_HIP(hipMemcpyAsync(s->d_wrench, s->h_wrench, 6 * nn * sizeof(float), hipMemcpyHostToDevice, s->stream));
-        SC_HIP(hipMemcpyAsync(s->dev.wlast, s->h_wlast, nn * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+        MW_HIP(hipMemcpyAsync(s->d_wrench.get(), s->h_wrench.get(), 6 * nn * sizeof(float), hipMemcpyHostToDevice,
+                              s->stream));
+        MW_HIP(hipMemcpyAsync(s->dev.wlast, s->h_wlast.get(), nn * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
     }
     if (s->pid_dirty) {
         for (int d = 0; d < s->NB; ++d) {
@@ -464,7 +463,8 @@ int flush(mw_scene* s, bool defer, bool direct = false) {
             s->h_pid[d] = {to_f32(g[0]), to_f32(g[1]), to_f32(g[2]), to_f32(g[7]), to_f32(g[6]),
                            to_f32(g[4]), to_f32(g[3]), to_f32(g[5])};
         }
-        SC_HIP(hipMemcpyAsync(s->d_pid, s->h_pid, NBMAX * sizeof(mw::PidF), hipMemcpyHostToDevice, s->stream));
+        MW_HIP(hipMemcpyAsync(s->d_pid.get(), s->h_pid.get(), NBMAX * sizeof(mw::PidF), hipMemcpyHostToDevice,
+                              s->stream));
     }
     s->idle = false;
     s->cmd_dirty = s->base_dirty = s->present_dirty = s->wrench_dirty = s->pid_dirty = false;
@@ -511,29 +511,31 @@ int ensure_big(mw_scene* s) {
     const int64_t stride = rows ? mw::sc_big_world_floats(cmax, rows, maxnv) : 0;
     const size_t bytes = static_cast<size_t>(stride) * s->W * sizeof(float);
     if (bytes != s->big_bytes) {
-        (void)hipFree(s->d_big);
-        s->d_big = nullptr;
-        s->big_bytes = 0;
-        if (bytes) SC_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_big), bytes));
+        // the new buffer first: a failure leaves the old one and its view valid
+        mw::dev_ptr<float[]> big;
+        if (bytes) MW_HIP(mw::dev_alloc(big, bytes));
+        s->d_big = std::move(big);
         s->big_bytes = bytes;
     }
     mw::SceneDev& D = s->dev;
-    D.big = rows ? s->d_big : nullptr;
+    D.big = rows ? s->d_big.get() : nullptr;
     D.big_stride = stride;
     D.big_cmax = cmax;
     D.big_rows = rows;
     const int cap = std::max(CMAX, cmax);
     if (cap != s->contact_cap) {
         const size_t n = static_cast<size_t>(cap) * 12 * s->W * sizeof(float);
-        (void)hipFree(s->d_contact);
-        (void)hipHostFree(s->h_contact);
-        s->d_contact = nullptr;
-        s->h_contact = nullptr;
-        SC_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_contact), n));
-        SC_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_contact), n, hipHostMallocDefault));
+        // both new buffers first, then the swap: a failure leaves the old pair,
+        // dev.contact and contact_cap as they were
+        mw::dev_ptr<float[]> dc;
+        mw::pin_ptr<float[]> hc;
+        MW_HIP(mw::dev_alloc(dc, n));
+        MW_HIP(mw::pin_alloc(hc, n));
+        s->d_contact = std::move(dc);
+        s->h_contact = std::move(hc);
         s->contact_cap = cap;
-        D.contact = s->d_contact;
-        SC_HIP(hipMemsetAsync(D.ncontact, 0, s->W * sizeof(int32_t), s->stream));
+        D.contact = s->d_contact.get();
+        MW_HIP(hipMemsetAsync(D.ncontact, 0, s->W * sizeof(int32_t), s->stream));
     }
     D.contact_cap = cap;
     return MW_OK;
@@ -543,14 +545,15 @@ int queue_readback(mw_scene* s, bool base = true) {
     const size_t plane = s->jrows * sizeof(float), rows = static_cast<size_t>(s->NB) * s->W * sizeof(float);
     if (rows && 3 * plane <= (size_t{1} << 20)) {
         // small scenes: one copy of the three planes beats three copies
-        SC_HIP(hipMemcpyAsync(s->h_joint, s->d_joint, 3 * plane, hipMemcpyDeviceToHost, s->stream));
+        MW_HIP(hipMemcpyAsync(s->h_joint.get(), s->d_joint.get(), 3 * plane, hipMemcpyDeviceToHost, s->stream));
     } else if (rows) {
         for (int f = 0; f < 3; ++f)
-            SC_HIP(hipMemcpyAsync(s->h_joint + f * plane, static_cast<uint8_t*>(s->d_joint) + f * plane, rows,
-                                  hipMemcpyDeviceToHost, s->stream));
+            MW_HIP(hipMemcpyAsync(s->h_joint.get() + f * plane, static_cast<uint8_t*>(s->d_joint.get()) + f * plane,
+                                  rows, hipMemcpyDeviceToHost, s->stream));
     }
     const size_t brows = static_cast<size_t>(13 * s->models.size()) * s->W * sizeof(float);
-    if (brows && base) SC_HIP(hipMemcpyAsync(s->h_base, s->d_base, brows, hipMemcpyDeviceToHost, s->stream));
+    if (brows && base) MW_HIP(hipMemcpyAsync(s->h_base.get(), s->d_base.get(), brows, hipMemcpyDeviceToHost,
+                                             s->stream));
     s->idle = false;
     return MW_OK;
 }
@@ -567,9 +570,11 @@ int pull_base(mw_scene* s) { return pull_joints(s); }
 
 int pull_contacts(mw_scene* s) {
     if (!s->contacts_stale) return MW_OK;
-    SC_HIP(hipMemcpyAsync(s->h_ncontact, s->dev.ncontact, s->W * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
-    SC_HIP(hipMemcpyAsync(s->h_contact, s->d_contact, static_cast<size_t>(s->contact_cap) * 12 * s->W * sizeof(float),
-                          hipMemcpyDeviceToHost, s->stream));
+    MW_HIP(hipMemcpyAsync(s->h_ncontact.get(), s->dev.ncontact, s->W * sizeof(int32_t), hipMemcpyDeviceToHost,
+                          s->stream));
+    MW_HIP(hipMemcpyAsync(s->h_contact.get(), s->d_contact.get(),
+                          static_cast<size_t>(s->contact_cap) * 12 * s->W * sizeof(float), hipMemcpyDeviceToHost,
+                          s->stream));
     if (int rc = sync(s)) return rc;
     s->contacts_stale = false;
     return MW_OK;
@@ -589,37 +594,12 @@ int selection(const mw_scene* s, int32_t w0, int32_t nw, const int32_t* dofs, in
     return MW_OK;
 }
 
-int copy_str(const std::string& v, char* buf, int32_t len) {
-    if (!buf || len <= 0) return fail(MW_EINVAL, "invalid output buffer");
-    if (static_cast<int32_t>(v.size()) + 1 > len) return fail(MW_EINVAL, "output buffer too small");
-    std::memcpy(buf, v.c_str(), v.size() + 1);
-    return MW_OK;
-}
-
-// quaternion wxyz of a row-major rotation
-void quat_of(const std::array<double, 9>& R, double q[4]) {
-    const double tr = R[0] + R[4] + R[8];
-    if (tr > 0) {
-        const double k = 0.5 / std::sqrt(tr + 1.0);
-        q[0] = 0.25 / k; q[1] = (R[7] - R[5]) * k; q[2] = (R[2] - R[6]) * k; q[3] = (R[3] - R[1]) * k;
-    } else if (R[0] > R[4] && R[0] > R[8]) {
-        const double k = 2.0 * std::sqrt(1.0 + R[0] - R[4] - R[8]);
-        q[0] = (R[7] - R[5]) / k; q[1] = 0.25 * k; q[2] = (R[1] + R[3]) / k; q[3] = (R[2] + R[6]) / k;
-    } else if (R[4] > R[8]) {
-        const double k = 2.0 * std::sqrt(1.0 + R[4] - R[0] - R[8]);
-        q[0] = (R[2] - R[6]) / k; q[1] = (R[1] + R[3]) / k; q[2] = 0.25 * k; q[3] = (R[5] + R[7]) / k;
-    } else {
-        const double k = 2.0 * std::sqrt(1.0 + R[8] - R[0] - R[4]);
-        q[0] = (R[3] - R[1]) / k; q[1] = (R[2] + R[6]) / k; q[2] = (R[5] + R[7]) / k; q[3] = 0.25 * k;
-    }
-}
-
 // model m enters worlds [w0, w0 + nw) at its insertion pose, joints at rest
 // A reset, insertion or removal of a world's models re-arms its divergence
 // flag (mwscene.h): a world that diverged, was reset and diverges again is
 // reported again.
 int rearm_diverged(mw_scene* s, int32_t w0, int32_t nw) {
-    if (s->dev.diverged && nw > 0) SC_HIP(hipMemsetAsync(s->dev.diverged + w0, 0, nw, s->stream));
+    if (s->dev.diverged && nw > 0) MW_HIP(hipMemsetAsync(s->dev.diverged + w0, 0, nw, s->stream));
     return MW_OK;
 }
 
@@ -627,7 +607,7 @@ int place_model(mw_scene* s, int m, int32_t w0, int32_t nw) {
     if (int rc = pull_joints(s)) return rc;
     const SceneModel& sm = s->models[m];
     double q[4];
-    quat_of(sm.m.base_R, q);
+    mw::quat_of(sm.m.base_R, q);
     const double init[13] = {sm.m.base_p[0], sm.m.base_p[1], sm.m.base_p[2], q[0], q[1], q[2], q[3], 0, 0, 0, 0, 0, 0};
     for (int w = w0; w < w0 + nw; ++w) {
         s->h_present[w] |= 1u << m;
@@ -674,65 +654,60 @@ int mw_scene_create(const mw_config* cfg, mw_scene** out) {
     if (s->cfg.pgs_iters <= 0) s->cfg.pgs_iters = 50;
     s->W = cfg->n_worlds;
     s->dt_ns = static_cast<int64_t>(std::llround(cfg->step_size * 1e9));
-    SC_HIP(hipSetDevice(cfg->device));
-    SC_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    s->own_stream = true;
+    MW_HIP(hipSetDevice(cfg->device));
+    MW_HIP(mw::stream_create(s->own_stream, hipStreamNonBlocking));
+    s->stream = s->own_stream.get();
     const size_t W = static_cast<size_t>(s->W);
     s->jrows = static_cast<size_t>(NBMAX) * W;
-    SC_HIP(hipMalloc(&s->d_joint, s->joint_bytes()));
-    SC_HIP(hipMemsetAsync(s->d_joint, 0, s->joint_bytes(), s->stream));
+    MW_HIP(mw::dev_alloc(s->d_joint, s->joint_bytes()));
+    MW_HIP(hipMemsetAsync(s->d_joint.get(), 0, s->joint_bytes(), s->stream));
     // coherent: direct runs read the command block out of it and write the
     // joint planes into it (scene_run)
-    SC_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_joint), s->cmd_off() + s->cmd_bytes(),
-                         hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(s->h_joint, 0, s->cmd_off() + s->cmd_bytes());
+    MW_HIP(mw::pin_alloc(s->h_joint, s->cmd_off() + s->cmd_bytes(), hipHostMallocMapped | hipHostMallocCoherent));
+    std::memset(s->h_joint.get(), 0, s->cmd_off() + s->cmd_bytes());
     {
         void* dptr = nullptr;
-        if (hipHostGetDevicePointer(&dptr, s->h_joint, 0) == hipSuccess) s->h_joint_dev = static_cast<float*>(dptr);
+        if (hipHostGetDevicePointer(&dptr, s->h_joint.get(), 0) == hipSuccess)
+            s->h_joint_dev = static_cast<float*>(dptr);
         else (void)hipGetLastError();
     }
-    SC_HIP(hipMalloc(&s->d_base, s->base_bytes()));
-    SC_HIP(hipMemsetAsync(s->d_base, 0, s->base_bytes(), s->stream));
-    SC_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_base), s->base_bytes(), hipHostMallocDefault));
-    std::memset(s->h_base, 0, s->base_bytes());
+    MW_HIP(mw::dev_alloc(s->d_base, s->base_bytes()));
+    MW_HIP(hipMemsetAsync(s->d_base.get(), 0, s->base_bytes(), s->stream));
+    MW_HIP(mw::pin_alloc(s->h_base, s->base_bytes()));
+    std::memset(s->h_base.get(), 0, s->base_bytes());
     const size_t nwl = static_cast<size_t>(SLOTS) * NNMAX * W;
     const size_t misc = W * sizeof(uint32_t) + W * sizeof(int32_t) + 64 + nwl * sizeof(int32_t) + W;
-    SC_HIP(hipMalloc(&s->d_misc, misc));
-    SC_HIP(hipMemsetAsync(s->d_misc, 0, misc, s->stream));
-    SC_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_wrench), 6 * nwl * sizeof(float)));
-    SC_HIP(hipMemsetAsync(s->d_wrench, 0, 6 * nwl * sizeof(float), s->stream));
-    SC_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_contact), static_cast<size_t>(CMAX) * 12 * W * sizeof(float)));
-    SC_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_pid), NBMAX * sizeof(mw::PidF)));
-    SC_HIP(hipMalloc(reinterpret_cast<void**>(&s->dp), sizeof(mw::SceneF)));
-    SC_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_wphys), 4 * W * sizeof(float)));
-    SC_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_warm), mw::kScWarmWords * W * sizeof(int32_t)));
-    SC_HIP(hipMemsetAsync(s->d_warm, 0, mw::kScWarmWords * W * sizeof(int32_t), s->stream));
-    SC_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_wphys), 4 * W * sizeof(float), hipHostMallocDefault));
+    MW_HIP(mw::dev_alloc(s->d_misc, misc));
+    MW_HIP(hipMemsetAsync(s->d_misc.get(), 0, misc, s->stream));
+    MW_HIP(mw::dev_alloc(s->d_wrench, 6 * nwl * sizeof(float)));
+    MW_HIP(hipMemsetAsync(s->d_wrench.get(), 0, 6 * nwl * sizeof(float), s->stream));
+    MW_HIP(mw::dev_alloc(s->d_contact, static_cast<size_t>(CMAX) * 12 * W * sizeof(float)));
+    MW_HIP(mw::dev_alloc(s->d_pid, NBMAX * sizeof(mw::PidF)));
+    MW_HIP(mw::dev_alloc(s->dp, sizeof(mw::SceneF)));
+    MW_HIP(mw::dev_alloc(s->d_wphys, 4 * W * sizeof(float)));
+    MW_HIP(mw::dev_alloc(s->d_warm, mw::kScWarmWords * W * sizeof(int32_t)));
+    MW_HIP(hipMemsetAsync(s->d_warm.get(), 0, mw::kScWarmWords * W * sizeof(int32_t), s->stream));
+    MW_HIP(mw::pin_alloc(s->h_wphys, 4 * W * sizeof(float)));
     for (size_t w = 0; w < W; ++w) {
         for (int k = 0; k < 3; ++k) s->h_wphys[k * W + w] = static_cast<float>(s->gravity[k]);
         s->h_wphys[3 * W + w] = static_cast<float>(s->mu);
     }
-    SC_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_present), W * sizeof(uint32_t), hipHostMallocDefault));
-    std::memset(s->h_present, 0, W * sizeof(uint32_t));
-    SC_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_wlast), nwl * sizeof(int32_t), hipHostMallocDefault));
-    std::fill(s->h_wlast, s->h_wlast + nwl, -1);
-    SC_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_wrench), 6 * nwl * sizeof(float), hipHostMallocDefault));
-    std::memset(s->h_wrench, 0, 6 * nwl * sizeof(float));
-    SC_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_contact), static_cast<size_t>(CMAX) * 12 * W * sizeof(float),
-                         hipHostMallocDefault));
-    SC_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_ncontact), W * sizeof(int32_t), hipHostMallocDefault));
-    std::memset(s->h_ncontact, 0, W * sizeof(int32_t));
-    if (!s->h_overflow) {
-        SC_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_overflow), sizeof(int32_t), hipHostMallocDefault));
-        *s->h_overflow = 0;
-    }
-    if (!s->h_ndiv) {
-        SC_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_ndiv), sizeof(uint64_t), hipHostMallocDefault));
-        *s->h_ndiv = 0;
-    }
-    SC_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_pid), NBMAX * sizeof(mw::PidF), hipHostMallocDefault));
+    MW_HIP(mw::pin_alloc(s->h_present, W * sizeof(uint32_t)));
+    std::memset(s->h_present.get(), 0, W * sizeof(uint32_t));
+    MW_HIP(mw::pin_alloc(s->h_wlast, nwl * sizeof(int32_t)));
+    std::fill(s->h_wlast.get(), s->h_wlast.get() + nwl, -1);
+    MW_HIP(mw::pin_alloc(s->h_wrench, 6 * nwl * sizeof(float)));
+    std::memset(s->h_wrench.get(), 0, 6 * nwl * sizeof(float));
+    MW_HIP(mw::pin_alloc(s->h_contact, static_cast<size_t>(CMAX) * 12 * W * sizeof(float)));
+    MW_HIP(mw::pin_alloc(s->h_ncontact, W * sizeof(int32_t)));
+    std::memset(s->h_ncontact.get(), 0, W * sizeof(int32_t));
+    MW_HIP(mw::pin_alloc(s->h_overflow, sizeof(int32_t)));
+    *s->h_overflow = 0;
+    MW_HIP(mw::pin_alloc(s->h_ndiv, sizeof(uint64_t)));
+    *s->h_ndiv = 0;
+    MW_HIP(mw::pin_alloc(s->h_pid, NBMAX * sizeof(mw::PidF)));
     // device views
-    float* j = static_cast<float*>(s->d_joint);
+    float* j = static_cast<float*>(s->d_joint.get());
     const size_t r = s->jrows;
     mw::SceneDev& D = s->dev;
     D.q = j; D.qd = j + r; D.qdd = j + 2 * r;
@@ -741,68 +716,37 @@ int mw_scene_create(const mw_config* cfg, mw_scene** out) {
     D.rflag = D.act + r;
     float* tail = reinterpret_cast<float*>(D.rflag + r);
     D.pid_e = tail; D.pid_i = tail + r; D.pid_u = tail + 2 * r;
-    float* b = static_cast<float*>(s->d_base);
+    float* b = static_cast<float*>(s->d_base.get());
     const size_t kr = s->krows();
     D.base = b; D.rpose = b + 13 * kr; D.rvel = b + 20 * kr;
     D.bflag = reinterpret_cast<uint8_t*>(b + 26 * kr);
-    uint8_t* mp = static_cast<uint8_t*>(s->d_misc);
+    uint8_t* mp = static_cast<uint8_t*>(s->d_misc.get());
     D.present = reinterpret_cast<uint32_t*>(mp);
     D.ncontact = reinterpret_cast<int32_t*>(mp + W * sizeof(uint32_t));
     D.overflow = reinterpret_cast<int32_t*>(mp + W * sizeof(uint32_t) + W * sizeof(int32_t));
     D.wlast = reinterpret_cast<int32_t*>(mp + W * sizeof(uint32_t) + W * sizeof(int32_t) + 64);
     D.diverged = mp + W * sizeof(uint32_t) + W * sizeof(int32_t) + 64 + nwl * sizeof(int32_t);
-    D.wrench = s->d_wrench;
-    D.contact = s->d_contact;
+    D.wrench = s->d_wrench.get();
+    D.contact = s->d_contact.get();
     D.contact_cap = CMAX;
-    D.big = nullptr;
-    D.big_stride = 0;
-    D.big_cmax = D.big_rows = 0;
-    D.wphys = s->d_wphys;
-    D.warm = s->d_warm;
+    D.wphys = s->d_wphys.get();
+    D.warm = s->d_warm.get();
     s->mode.assign(s->jrows, MW_MODE_IDLE);
     s->cmd64.assign(s->jrows, 0.0);
     s->ptgt64.assign(s->jrows, 0.0);
     s->wrench_dirty = true;
-    SC_HIP(hipStreamSynchronize(s->stream));
+    MW_HIP(hipStreamSynchronize(s->stream));
     *out = s.release();
     return MW_OK;
 }
 
-void mw_scene_destroy(mw_scene* s) {
-    if (!s) return;
-    (void)hipSetDevice(s->cfg.device);
-    if (s->stream) (void)hipStreamSynchronize(s->stream);
-    (void)hipFree(s->d_joint);
-    (void)hipFree(s->d_base);
-    (void)hipFree(s->d_misc);
-    (void)hipFree(s->d_wrench);
-    (void)hipFree(s->d_contact);
-    (void)hipFree(s->d_big);
-    (void)hipFree(s->d_pid);
-    (void)hipFree(s->dp);
-    (void)hipFree(s->d_wphys);
-    (void)hipFree(s->d_warm);
-    (void)hipHostFree(s->h_wphys);
-    (void)hipHostFree(s->h_joint);
-    (void)hipHostFree(s->h_base);
-    (void)hipHostFree(s->h_present);
-    (void)hipHostFree(s->h_wlast);
-    (void)hipHostFree(s->h_wrench);
-    (void)hipHostFree(s->h_contact);
-    (void)hipHostFree(s->h_ncontact);
-    (void)hipHostFree(s->h_overflow);
-    (void)hipHostFree(s->h_ndiv);
-    (void)hipHostFree(s->h_pid);
-    if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
-    delete s;
-}
+void mw_scene_destroy(mw_scene* s) { delete s; }
 
 int mw_scene_set_stream(mw_scene* s, void* stream) {
     if (int rc = check(s)) return rc;
-    SC_HIP(hipStreamSynchronize(s->stream));
-    if (s->own_stream) (void)hipStreamDestroy(s->stream);
+    MW_HIP(hipStreamSynchronize(s->stream));
+    s->own_stream.reset();
     s->stream = static_cast<hipStream_t>(stream);
-    s->own_stream = false;
     return MW_OK;
 }
 
@@ -1063,7 +1007,7 @@ static int scene_run(mw_scene* s, int32_t paused, bool defer, bool direct = fals
                 }
             }
         }
-        SC_HIP(mw::launch_scene_run(s->dp, s->nv, D, s->d_pid, G, s->W, a, s->stream));
+        MW_HIP(mw::launch_scene_run(s->dp.get(), s->nv, D, s->d_pid.get(), G, s->W, a, s->stream));
         s->idle = false;
         a.first = 0;
         done += chunk;
@@ -1085,14 +1029,14 @@ int mw_scene_run(mw_scene* s, int32_t paused) {
     // the joint and base state are queued back to back
     // small scenes (the per-env path, BASELINE config 1) run direct: no
     // command upload, no joint readback copy -- one launch, one synchronisation
-    const bool direct = s->h_joint_dev && 3 * s->jrows * sizeof(float) <= kDirectBytes;
+    const bool direct = s && s->h_joint_dev && 3 * s->jrows * sizeof(float) <= kDirectBytes;
     if (int rc = scene_run(s, paused, true, direct)) return rc;
     if (s->models.empty()) return MW_OK;
     // per-env runs: skip the copies that cannot carry news
     if (direct) {
         const size_t brows = static_cast<size_t>(13 * s->models.size()) * s->W * sizeof(float);
         if (brows && needs_base_readback(s))
-            SC_HIP(hipMemcpyAsync(s->h_base, s->d_base, brows, hipMemcpyDeviceToHost, s->stream));
+            MW_HIP(hipMemcpyAsync(s->h_base.get(), s->d_base.get(), brows, hipMemcpyDeviceToHost, s->stream));
     } else if (int rc = queue_readback(s, needs_base_readback(s))) {
         return rc;
     }
@@ -1100,9 +1044,10 @@ int mw_scene_run(mw_scene* s, int32_t paused) {
     // divergence count of the larger scenes (a direct run's state is in the
     // pinned mirror already: it is checked there, below)
     if (can_overflow(s))
-        SC_HIP(hipMemcpyAsync(s->h_overflow, s->dev.overflow, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+        MW_HIP(hipMemcpyAsync(s->h_overflow.get(), s->dev.overflow, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
     if (!direct)
-        SC_HIP(hipMemcpyAsync(s->h_ndiv, s->dev.overflow + 4, sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+        MW_HIP(hipMemcpyAsync(s->h_ndiv.get(), s->dev.overflow + 4, sizeof(uint64_t), hipMemcpyDeviceToHost,
+                              s->stream));
     if (int rc = sync(s)) return rc;
     clear_consumed(s);
     s->joints_stale = s->base_stale = false;
@@ -1110,15 +1055,16 @@ int mw_scene_run(mw_scene* s, int32_t paused) {
         // the kernel flags a world whose stored state is not finite; a direct
         // run reads the count only when its mirror holds such a value
         bool bad = false;
-        const uint32_t* jb = reinterpret_cast<const uint32_t*>(s->h_joint);
+        const uint32_t* jb = reinterpret_cast<const uint32_t*>(s->h_joint.get());
         for (size_t k = 0; k < 2 * s->jrows && !bad; ++k) bad = (jb[k] & 0x7f800000u) == 0x7f800000u;
         if (!bad && needs_base_readback(s)) {
-            const uint32_t* bb = reinterpret_cast<const uint32_t*>(s->h_base);
+            const uint32_t* bb = reinterpret_cast<const uint32_t*>(s->h_base.get());
             const size_t nb = static_cast<size_t>(13 * s->models.size()) * s->W;
             for (size_t k = 0; k < nb && !bad; ++k) bad = (bb[k] & 0x7f800000u) == 0x7f800000u;
         }
         if (bad) {
-            SC_HIP(hipMemcpyAsync(s->h_ndiv, s->dev.overflow + 4, sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+            MW_HIP(hipMemcpyAsync(s->h_ndiv.get(), s->dev.overflow + 4, sizeof(uint64_t), hipMemcpyDeviceToHost,
+                                  s->stream));
             if (int rc = sync(s)) return rc;
         }
     }
@@ -1147,10 +1093,10 @@ int mw_scene_run(mw_scene* s, int32_t paused) {
 int mw_scene_diverged(mw_scene* s, int32_t w0, int32_t nw, uint8_t* flags, int64_t* count) {
     if (int rc = check(s)) return rc;
     if (int rc = check_worlds(s, w0, nw)) return rc;
-    if (flags && nw) SC_HIP(hipMemcpyAsync(flags, s->dev.diverged + w0, nw, hipMemcpyDeviceToHost, s->stream));
+    if (flags && nw) MW_HIP(hipMemcpyAsync(flags, s->dev.diverged + w0, nw, hipMemcpyDeviceToHost, s->stream));
     uint64_t n = 0;
-    SC_HIP(hipMemcpyAsync(&n, s->dev.overflow + 4, sizeof(n), hipMemcpyDeviceToHost, s->stream));
-    SC_HIP(hipStreamSynchronize(s->stream));
+    MW_HIP(hipMemcpyAsync(&n, s->dev.overflow + 4, sizeof(n), hipMemcpyDeviceToHost, s->stream));
+    MW_HIP(hipStreamSynchronize(s->stream));
     if (count) *count = static_cast<int64_t>(n);
     return MW_OK;
 }
@@ -1158,7 +1104,7 @@ int mw_scene_diverged(mw_scene* s, int32_t w0, int32_t nw, uint8_t* flags, int64
 int mw_scene_clear_diverged(mw_scene* s, int32_t w0, int32_t nw) {
     if (int rc = check(s)) return rc;
     if (int rc = check_worlds(s, w0, nw)) return rc;
-    if (nw) SC_HIP(hipMemsetAsync(s->dev.diverged + w0, 0, nw, s->stream));
+    if (nw) MW_HIP(hipMemsetAsync(s->dev.diverged + w0, 0, nw, s->stream));
     return MW_OK;
 }
 
@@ -1449,7 +1395,7 @@ int mw_scene_get_base_pose(const mw_scene* cs, int32_t model, int32_t w0, int32_
     for (int w = 0; w < nw; ++w) {
         if (!sm.m.floating) {
             double q[4];
-            quat_of(sm.m.base_R, q);
+            mw::quat_of(sm.m.base_R, q);
             const double v[7] = {sm.m.base_p[0], sm.m.base_p[1], sm.m.base_p[2], q[0], q[1], q[2], q[3]};
             for (int f = 0; f < 7; ++f) out[w * 7 + f] = v[f];
         } else {
@@ -1595,8 +1541,8 @@ int mw_scene_lcp_unconverged(const mw_scene* s, int64_t* world_steps) {
     if (int rc = check(s)) return rc;
     if (!world_steps) return fail(MW_EINVAL, "null argument");
     uint64_t v = 0;
-    SC_HIP(hipMemcpyAsync(&v, s->dev.overflow + 2, sizeof(v), hipMemcpyDeviceToHost, s->stream));
-    SC_HIP(hipStreamSynchronize(s->stream));
+    MW_HIP(hipMemcpyAsync(&v, s->dev.overflow + 2, sizeof(v), hipMemcpyDeviceToHost, s->stream));
+    MW_HIP(hipStreamSynchronize(s->stream));
     *world_steps = static_cast<int64_t>(v);
     return MW_OK;
 }
@@ -1605,8 +1551,8 @@ int mw_scene_overflow(const mw_scene* s, int64_t* dropped) {
     if (int rc = check(s)) return rc;
     if (!dropped) return fail(MW_EINVAL, "null argument");
     int v = 0;
-    SC_HIP(hipMemcpyAsync(&v, s->dev.overflow, sizeof(int), hipMemcpyDeviceToHost, s->stream));
-    SC_HIP(hipStreamSynchronize(s->stream));
+    MW_HIP(hipMemcpyAsync(&v, s->dev.overflow, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    MW_HIP(hipStreamSynchronize(s->stream));
     *dropped = v;
     return MW_OK;
 }
@@ -1652,8 +1598,8 @@ extern "C" int mw_debug_scene_big_ws(mw_scene* s, int32_t w, float* out, int64_t
     if (!D.big) return MW_OK;
     const int64_t n = std::min<int64_t>(cap, static_cast<int64_t>(mw::kScBigContactWords) * D.big_cmax +
                                                   11LL * D.big_rows);
-    SC_HIP(hipStreamSynchronize(s->stream));
-    SC_HIP(hipMemcpy(out, D.big + static_cast<size_t>(w) * static_cast<size_t>(D.big_stride), n * sizeof(float),
+    MW_HIP(hipStreamSynchronize(s->stream));
+    MW_HIP(hipMemcpy(out, D.big + static_cast<size_t>(w) * static_cast<size_t>(D.big_stride), n * sizeof(float),
                      hipMemcpyDeviceToHost));
     return MW_OK;
 }

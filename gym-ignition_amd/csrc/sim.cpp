@@ -12,7 +12,6 @@
 #include <algorithm>
 #include <array>
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <limits>
@@ -22,192 +21,60 @@
 #include <vector>
 
 #include "baked_models.hpp"
-#include "chain_params.hpp"
-#include "float_task.hpp"
-#include "float_tree.hpp"
-#include "free_body.hpp"
-#include "kernels.hpp"
-#include "model.hpp"
 #include "errors.hpp"
+#include "sim_state.hpp"
 
-namespace {
+using mw::copy_str;
+using mw::fail;
+using mw::kDefaultPid;
+using mw::to_f32;
 
-thread_local std::string g_last_error;
+static thread_local std::string g_last_error;
 
-int fail(int code, const std::string& msg) {
-    g_last_error = msg;
-    return code;
-}
-
-}  // namespace
-
-// the calling thread's last error (mw_last_error), shared with scene.cpp
+// the calling thread's last error (mw_last_error), shared with vecenv.cpp and scene.cpp
 void mw::set_last_error(const std::string& msg) { g_last_error = msg; }
 
-namespace {
-
-#define MW_HIP(call)                                                                      \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess)                                                             \
-            return fail(MW_EHIP, std::string(#call " failed: ") + hipGetErrorString(e_)); \
-    } while (0)
-
-}  // namespace
-
-struct mw_sim {
-    mw_config cfg{};
-    bool own_stream = false;
-    bool stream_set = false;  // mw_set_stream called (NULL = the legacy default stream)
-    hipStream_t stream = nullptr;
-    bool loaded = false;
-    bool initialized = false;
-    bool stepped = false;     // model parameters become read-only after the first run
-    bool servo_used = false;  // a joint was put in VelocityFollowerDart
-    bool host_stale = false;  // device state changed by the VecEnv path
-    // a floating-base env (mw_floatenv_create) writes the commands and pending
-    // resets on the device: the host setters of either fail with MW_ESTATE
-    bool env_owned = false;
-    bool cmd_dirty = true;
-    bool ptgt_dirty = false;  // host position targets newer than the device copy
-    bool ptgt_stale = false;  // device position targets newer than the host mirror
-    bool ptgt_view = false;   // a device view of the targets was handed out (always re-read)
-    int topo = 0;             // kernel topology id (kernels.hpp: kernel_topology)
-    mw::ChainModel model;
-    std::string model_name;
-    double gravity[3] = {0.0, 0.0, -9.8};  // sdformat default world gravity
-    int64_t iterations = 0;
-    int64_t dt_ns = 0;
-    // JointController (one per model): Model.cpp:181-185 initialises the period
-    // to the maximum duration; the plugin is inserted by the first Position /
-    // Velocity / VelocityFollowerDart joint (Joint.cpp:376-404)
-    bool controller = false;
-    int64_t period_ns = std::numeric_limits<int64_t>::max();
-    int64_t prev_ns = 0;      // JointController prevUpdateTime (0 = first iteration)
-    // JointPID per dof in scenario::core::PID order {p, i, d, cmdMin, cmdMax,
-    // cmdOffset, iMin, iMax}; default = Joint.cpp:63 DefaultPID
-    std::vector<std::array<double, 8>> pid;
-
-    int n = 0, W = 0;
-    size_t nw = 0;  // n * W
-    // device block layout: [q qd qdd | cmd vtgt rq rqd | act rflag]; the host
-    // mirror has the same layout so the command slab moves in one copy
-    void* d_block = nullptr;
-    uint8_t* h_block = nullptr;
-    size_t block_bytes = 0, cmd_off = 0, cmd_bytes = 0, state_bytes = 0;
-    mw::ChainF* d_params = nullptr;
-    mw::ChainF h_params{};
-    // [ptgt | pid_e | pid_i | pid_u | qlo] on the device; h_ptgt mirrors ptgt
-    float* d_aux = nullptr;
-    float* h_ptgt = nullptr;
-    // pinned staging copy of [command slab | position targets]: the H2D copies
-    // of a run read it, so the host mirror can be cleared / rewritten right
-    // after the launch; stage_ev marks when the last copy out of it finished
-    uint8_t* h_stage = nullptr;
-    hipEvent_t stage_ev = nullptr;
-    bool stage_pending = false;
-    // floating single-body models (free_body.hpp)
-    bool floating = false;
-    bool ground = false;          // a ground plane z = 0 is in the world
-    double ground_mu = 1.0;       // SDF <surface><friction><ode><mu> default
-    bool contacts = false;        // Model::enableContacts
-    mw::FreeF h_free{};
-    mw::FreeF* d_free = nullptr;
-    mw::FreeDev fdev{};
-    void* d_fblock = nullptr;     // [base 13 | rpose 7 | rvel 6 | contacts 7*slots][W] f32 + rflag u8 + cmask u32
-    float* h_base = nullptr;      // [13][W] host mirror (pinned)
-    float* h_cdata = nullptr;     // [slots][7][W]
-    uint32_t* h_cmask = nullptr;  // [W]
-    std::vector<float> h_rpose, h_rvel;
-    std::vector<uint8_t> h_rflag;
-    bool free_dirty = false;
-    bool contacts_stale = false;  // contacts written on the device by mw_run_device
-    // articulated models on a floating base (float_tree.hpp): the joint state
-    // of a fixed-base model plus the base block above
-    bool float_tree = false;
-    // a fixed-base tree outside the compiled chain topologies (more than 9
-    // dofs, or branched other than the Panda): the world-per-wavefront kernel
-    // with a welded base (FloatF::fixed); its joint and base state live where a
-    // floating tree's do
-    bool fixed_tree = false;
-    bool fbase() const { return floating || fixed_tree; }
-    mw::FloatF h_float{};
-    mw::FloatF* d_float = nullptr;
-    float* d_ws = nullptr;        // constraint-row workspace [words][W]
-    int n_slots = mw::kMaxFreeSlots;
-    std::vector<int32_t> slot_body;  // body of every contact slot (-1 = base)
-    // large trees (or MWSTEP_WAVE_TREE=1): one world per wavefront (wave_tree.hpp)
-    bool wave = false;
-    bool wave_depth_ok = false;   // the tree fits the wave kernel's depth stack
-    int wave_depth = 0;           // the tree's depth in joints (picks the wave kernel's instance)
-    mw::PidF* d_pid = nullptr;    // PID gains of every dof (device)
-    mw::PidF* h_pid = nullptr;    // pinned staging copy
-    bool pid_dirty = true;        // gains changed since the last upload
-    int* d_overflow = nullptr;    // constraint rows dropped by the wave kernel
-    float* d_warm = nullptr;      // wave kernel: previous step's PGS impulses [kWaveWarmWordsHost][W]
-    double pgs_tol = 0.0;         // mw_set_pgs_options
-    bool pgs_warm = false;
-    // world wrenches (mw_apply_link_wrench, wave kernel): host records
-    // [slot][6][node][W] / [slot][node][W], device copies, the last iteration
-    // any record covers
-    std::vector<float> h_wr;
-    std::vector<int32_t> h_wl;
-    float* d_ext = nullptr;        // [6][node][W]: the summed wrenches of one launch
-    float* h_ext = nullptr;        // pinned staging of d_ext
-    int64_t wr_until = 0;
-    int* h_overflow = nullptr;    // pinned copy read back with each synchronous run
-    int64_t overflow_seen = 0;    // drops already reported
-    // divergence detection: [W] sticky per-world flags + the uint64 count of
-    // worlds flagged (device), its pinned copy (read back with every
-    // synchronous run) and the flags already reported
-    uint8_t* d_health = nullptr;
-    uint64_t* h_ndiv = nullptr;
-    int64_t div_seen = 0;
-    int32_t lcp_mode = MW_LCP_EXACT;  // mw_set_lcp_solver (wave kernel)
-    int32_t lcp_solves = 48;          // linear-solve budget of the exact solve per step (r06: a random humanoid impact needed 25-32)
-    mw::SimDev dev;
-    // host-only component data
-    std::vector<int32_t> mode;      // JointControlMode per [d][w]
-    std::vector<double> ptgt;       // JointPositionTarget
-    std::vector<double> cmd64;      // JointForceCmd exactly as set (double)
-
-    float* hq() { return reinterpret_cast<float*>(h_block); }
-    float* hqd() { return hq() + nw; }
-    float* hqdd() { return hq() + 2 * nw; }
-    float* hcmd() { return hq() + 3 * nw; }
-    float* hvt() { return hq() + 4 * nw; }
-    float* hrq() { return hq() + 5 * nw; }
-    float* hrqd() { return hq() + 6 * nw; }
-    uint8_t* hact() { return h_block + 7 * nw * sizeof(float); }
-    uint8_t* hrflag() { return hact() + nw; }
-    size_t idx(int d, int w) const { return static_cast<size_t>(d) * W + w; }
-};
-
-struct mw_vecenv {
-    mw_sim* sim = nullptr;
-    mw_task_config cfg{};
-    mw::TaskF task{};
-    mw::VecDev dev{};
-    void* d_counters = nullptr;
-    void* d_physics = nullptr;  // per-world randomised masses + gravity
-    // lane-group Panda kernel: per-dof PID gains + reset pose (device), and
-    // the host copy last uploaded
-    mw::GLaneTask* d_lane = nullptr;
-    mw::GLaneTask h_lane[mw::kMaxKernelDofs] = {};
-    bool lane_uploaded = false;
-    // floating-base env (mw_floatenv_create): its task and sum a^2 per world
-    bool floatenv = false;
-    mw::FloatTaskF ftask{};
-    float* d_asq = nullptr;
-};
-
-namespace {
-
-int check_sim(const mw_sim* s, bool need_init = true) {
+int check_sim(const mw_sim* s, bool need_init) {
     if (!s) return fail(MW_EINVAL, "null simulator handle");
     if (need_init && !s->initialized) return fail(MW_ESTATE, "the simulator was not initialized");
     return MW_OK;
 }
+
+bool needs_cons(const mw_sim* s) {
+    return (s->h_params.flags & (mw::kHasLimits | mw::kHasFriction)) != 0 || s->servo_used;
+}
+bool needs_dual(const mw_sim* s) { return (s->h_params.flags & mw::kHasDamping) != 0; }
+
+// id of the shipped model whose float32 parameter block is bit-identical to the
+// loaded one (constant-folded kernels, baked_models.hpp), else 0.
+// MWSTEP_DISABLE_BAKED=1 forces the generic kernels.
+int baked_id(const mw_sim* s) {
+    const char* off = std::getenv("MWSTEP_DISABLE_BAKED");
+    if (off && *off && *off != '0') return 0;
+    const size_t words = 8 + 40 * static_cast<size_t>(s->n);
+    if (words * 4 == sizeof(mw::baked::kCartpoleHost) &&
+        std::memcmp(&s->h_params, &mw::baked::kCartpoleHost, words * 4) == 0)
+        return mw::baked::kCartpoleId;
+    if (words * 4 == sizeof(mw::baked::kPendulumHost) &&
+        std::memcmp(&s->h_params, &mw::baked::kPendulumHost, words * 4) == 0)
+        return mw::baked::kPendulumId;
+    if (words * 4 == sizeof(mw::baked::kPandaHost) &&
+        std::memcmp(&s->h_params, &mw::baked::kPandaHost, words * 4) == 0)
+        return mw::baked::kPandaId;
+    return 0;
+}
+
+mw::PidSet pid_set(const mw_sim* s) {
+    mw::PidSet P{};
+    for (int d = 0; d < s->n && d < mw::kMaxKernelDofs; ++d) {
+        const auto& g = s->pid[d];
+        P.g[d] = {to_f32(g[0]), to_f32(g[1]), to_f32(g[2]), to_f32(g[7]), to_f32(g[6]),
+                  to_f32(g[4]), to_f32(g[3]), to_f32(g[5])};
+    }
+    return P;
+}
+
+namespace {
 
 // Host setters of commands / pending resets on a simulator that a
 // floating-base env drives: the env writes the same device arrays from its
@@ -256,15 +123,10 @@ void build_params(mw_sim* s) {
         f.Io[5] = static_cast<float>(b.Ic[5] - b.mass * b.com[1] * b.com[2]);
         f.damping = static_cast<float>(b.damping);
         f.friction = static_cast<float>(b.friction);
-        auto clampf = [](double v) {
-            const double big = static_cast<double>(std::numeric_limits<float>::max());
-            // "unlimited" is FLT_MAX on the device (finite-math-only kernels)
-            return static_cast<float>(v > big ? big : (v < -big ? -big : v));
-        };
-        f.lower = clampf(b.lower);
-        f.upper = clampf(b.upper);
-        f.effort = clampf(b.effort);
-        f.vel_limit = clampf(b.vel_limit);
+        f.lower = to_f32(b.lower);
+        f.upper = to_f32(b.upper);
+        f.effort = to_f32(b.effort);
+        f.vel_limit = to_f32(b.vel_limit);
         f.limited = b.limited ? 1 : 0;
         f.parent = b.parent;
         if (b.damping != 0.0) flags |= mw::kHasDamping;
@@ -401,48 +263,24 @@ int upload_params(mw_sim* s) {
     if (s->float_tree) {
         build_params(s);
         build_float(s);
-        MW_HIP(hipMemcpyAsync(s->d_params, &s->h_params, sizeof(mw::ChainF), hipMemcpyHostToDevice, s->stream));
-        MW_HIP(hipMemcpyAsync(s->d_float, &s->h_float, sizeof(mw::FloatF), hipMemcpyHostToDevice, s->stream));
+        MW_HIP(hipMemcpyAsync(s->d_params.get(), &s->h_params, sizeof(mw::ChainF), hipMemcpyHostToDevice, s->stream));
+        MW_HIP(hipMemcpyAsync(s->d_float.get(), &s->h_float, sizeof(mw::FloatF), hipMemcpyHostToDevice, s->stream));
         return MW_OK;
     }
     if (s->floating) {
         build_free(s);
-        MW_HIP(hipMemcpyAsync(s->d_free, &s->h_free, sizeof(mw::FreeF), hipMemcpyHostToDevice, s->stream));
+        MW_HIP(hipMemcpyAsync(s->d_free.get(), &s->h_free, sizeof(mw::FreeF), hipMemcpyHostToDevice, s->stream));
         return MW_OK;
     }
     build_params(s);
-    MW_HIP(hipMemcpyAsync(s->d_params, &s->h_params, sizeof(mw::ChainF), hipMemcpyHostToDevice, s->stream));
+    MW_HIP(hipMemcpyAsync(s->d_params.get(), &s->h_params, sizeof(mw::ChainF), hipMemcpyHostToDevice, s->stream));
     return MW_OK;
-}
-
-bool needs_cons(const mw_sim* s) {
-    return (s->h_params.flags & (mw::kHasLimits | mw::kHasFriction)) != 0 || s->servo_used;
-}
-bool needs_dual(const mw_sim* s) { return (s->h_params.flags & mw::kHasDamping) != 0; }
-
-// id of the shipped model whose float32 parameter block is bit-identical to the
-// loaded one (constant-folded kernels, baked_models.hpp), else 0.
-// MWSTEP_DISABLE_BAKED=1 forces the generic kernels.
-int baked_id(const mw_sim* s) {
-    const char* off = std::getenv("MWSTEP_DISABLE_BAKED");
-    if (off && *off && *off != '0') return 0;
-    const size_t words = 8 + 40 * static_cast<size_t>(s->n);
-    if (words * 4 == sizeof(mw::baked::kCartpoleHost) &&
-        std::memcmp(&s->h_params, &mw::baked::kCartpoleHost, words * 4) == 0)
-        return mw::baked::kCartpoleId;
-    if (words * 4 == sizeof(mw::baked::kPendulumHost) &&
-        std::memcmp(&s->h_params, &mw::baked::kPendulumHost, words * 4) == 0)
-        return mw::baked::kPendulumId;
-    if (words * 4 == sizeof(mw::baked::kPandaHost) &&
-        std::memcmp(&s->h_params, &mw::baked::kPandaHost, words * 4) == 0)
-        return mw::baked::kPandaId;
-    return 0;
 }
 
 int pull_state(mw_sim* s) {
     if (!s->host_stale) return MW_OK;
     if (s->fbase()) {
-        MW_HIP(hipMemcpyAsync(s->h_base, s->fdev.base, 13 * static_cast<size_t>(s->W) * sizeof(float),
+        MW_HIP(hipMemcpyAsync(s->h_base.get(), s->fdev.base, 13 * static_cast<size_t>(s->W) * sizeof(float),
                               hipMemcpyDeviceToHost, s->stream));
         if (!s->float_tree) {
             MW_HIP(hipStreamSynchronize(s->stream));
@@ -450,7 +288,7 @@ int pull_state(mw_sim* s) {
             return MW_OK;
         }
     }
-    MW_HIP(hipMemcpyAsync(s->h_block, s->d_block, s->state_bytes, hipMemcpyDeviceToHost, s->stream));
+    MW_HIP(hipMemcpyAsync(s->h_block.get(), s->d_block.get(), s->state_bytes, hipMemcpyDeviceToHost, s->stream));
     MW_HIP(hipStreamSynchronize(s->stream));
     s->host_stale = false;
     return MW_OK;
@@ -459,31 +297,12 @@ int pull_state(mw_sim* s) {
 // position targets written on the device (mw_device_ptr) -> host mirror
 int pull_ptgt(mw_sim* s) {
     if (!s->ptgt_stale) return MW_OK;
-    MW_HIP(hipMemcpyAsync(s->h_ptgt, s->d_aux, s->nw * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    MW_HIP(hipMemcpyAsync(s->h_ptgt.get(), s->d_aux.get(), s->nw * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     MW_HIP(hipStreamSynchronize(s->stream));
     for (size_t k = 0; k < s->nw; ++k) s->ptgt[k] = s->h_ptgt[k];
     s->ptgt_stale = s->ptgt_view;
     return MW_OK;
 }
-
-float to_f32(double v) {
-    const double big = static_cast<double>(std::numeric_limits<float>::max());
-    return static_cast<float>(v > big ? big : (v < -big ? -big : v));
-}
-
-mw::PidSet pid_set(const mw_sim* s) {
-    mw::PidSet P{};
-    for (int d = 0; d < s->n && d < mw::kMaxKernelDofs; ++d) {
-        const auto& g = s->pid[d];
-        P.g[d] = {to_f32(g[0]), to_f32(g[1]), to_f32(g[2]), to_f32(g[7]), to_f32(g[6]),
-                  to_f32(g[4]), to_f32(g[3]), to_f32(g[5])};
-    }
-    return P;
-}
-
-// ignition::math::PID(1, 0.1, 0.01, -1, 0, -1, 0, 0) (Joint.cpp:63) as
-// {p, i, d, cmdMin, cmdMax, cmdOffset, iMin, iMax}
-constexpr std::array<double, 8> kDefaultPid = {1.0, 0.1, 0.01, 0.0, -1.0, 0.0, 0.0, -1.0};
 
 // resolve a (dofs, ndofs) selection; dofs == NULL -> all dofs
 int selection(const mw_sim* s, int32_t w0, int32_t nw, const int32_t* dofs, int32_t ndofs,
@@ -542,17 +361,6 @@ int rearm_diverged(mw_sim* s, int32_t w0, int32_t nw) {
     return MW_OK;
 }
 
-int copy_str(const std::string& v, char* buf, int32_t len) {
-    if (!buf || len <= 0) return fail(MW_EINVAL, "invalid output buffer");
-    if (static_cast<int32_t>(v.size()) + 1 > len) return fail(MW_EINVAL, "output buffer too small");
-    std::memcpy(buf, v.c_str(), v.size() + 1);
-    return MW_OK;
-}
-
-}  // namespace
-
-namespace {
-
 // the device rows of the per-world record (mw_get_state): {first row, rows},
 // every row W floats
 std::vector<std::pair<float*, int>> state_rows(const mw_sim* s) {
@@ -562,7 +370,7 @@ std::vector<std::pair<float*, int>> state_rows(const mw_sim* s) {
         v.push_back({s->dev.pid_e, 4 * s->n});   // pid_e, pid_i, pid_u, qlo
     }
     if (s->fbase()) v.push_back({s->fdev.base, 13});
-    if (s->d_warm) v.push_back({s->d_warm, mw::kWaveWarmWordsHost});
+    if (s->d_warm) v.push_back({s->d_warm.get(), mw::kWaveWarmWordsHost});
     return v;
 }
 
@@ -595,38 +403,7 @@ int mw_create(const mw_config* cfg, mw_sim** out) {
     return MW_OK;
 }
 
-void mw_destroy(mw_sim* s) {
-    if (!s) return;
-    if (s->initialized) {
-        (void)hipSetDevice(s->cfg.device);
-        if (s->stream) (void)hipStreamSynchronize(s->stream);
-        (void)hipFree(s->d_block);
-        (void)hipFree(s->d_params);
-        (void)hipFree(s->d_aux);
-        (void)hipHostFree(s->h_block);
-        (void)hipHostFree(s->h_ptgt);
-        (void)hipHostFree(s->h_stage);
-        if (s->stage_ev) (void)hipEventDestroy(s->stage_ev);
-        (void)hipFree(s->d_fblock);
-        (void)hipFree(s->d_free);
-        (void)hipFree(s->d_float);
-        (void)hipFree(s->d_ws);
-        (void)hipFree(s->d_pid);
-        (void)hipHostFree(s->h_pid);
-        (void)hipFree(s->d_overflow);
-        (void)hipFree(s->d_warm);
-        (void)hipFree(s->d_ext);
-        (void)hipHostFree(s->h_ext);
-        (void)hipHostFree(s->h_overflow);
-        (void)hipHostFree(s->h_base);
-        (void)hipHostFree(s->h_cdata);
-        (void)hipHostFree(s->h_cmask);
-        (void)hipFree(s->d_health);
-        (void)hipHostFree(s->h_ndiv);
-        if (s->own_stream) (void)hipStreamDestroy(s->stream);
-    }
-    delete s;
-}
+void mw_destroy(mw_sim* s) { delete s; }
 
 int mw_load_model(mw_sim* s, const char* urdf, const double pose[7], const char* name) {
     if (!s || !urdf) return fail(MW_EINVAL, "null argument");
@@ -703,17 +480,15 @@ int mw_load_model(mw_sim* s, const char* urdf, const double pose[7], const char*
     // the world-per-wavefront kernel only
     bool has_ball = false;
     for (const auto& b : s->model.bodies) has_ball = has_ball || b.ball != 0;
+    std::vector<int> parents;
+    for (const auto& b : s->model.bodies) parents.push_back(b.parent);
     if (!s->floating) {
         // fixed bases: the compiled chain topologies run on the lane kernels,
         // every other tree on the world-per-wavefront kernel with a welded base
-        std::vector<int> parents;
-        for (const auto& b : s->model.bodies) parents.push_back(b.parent);
         s->fixed_tree = s->model.dofs() > 9 || mw::kernel_topology(parents.data(), s->model.dofs()) < 0 || has_ball;
     }
     s->float_tree = (s->floating && (s->model.dofs() > 0 || free_wave)) || s->fixed_tree;
     if (s->float_tree) {
-        std::vector<int> parents;
-        for (const auto& b : s->model.bodies) parents.push_back(b.parent);
         s->topo = mw::kernel_topology(parents.data(), s->model.dofs());
         size_t n_shapes = s->fixed_tree ? 0 : s->model.base_shapes.size();
         bool damped = false;  // joint damping: the wave kernel (its dual recursion) only
@@ -778,14 +553,10 @@ int mw_load_model(mw_sim* s, const char* urdf, const double pose[7], const char*
         build_free(s);
         return MW_OK;
     }
-    {
-        std::vector<int> parents;
-        for (const auto& b : s->model.bodies) parents.push_back(b.parent);
-        s->topo = mw::kernel_topology(parents.data(), s->model.dofs());
-        if (s->topo < 0)
-            return fail(MW_EPARSE, "the kinematic topology of this branched model is not compiled into this "
-                                   "build (supported: serial chains of 1..9 dofs and the Panda tree)");
-    }
+    s->topo = mw::kernel_topology(parents.data(), s->model.dofs());
+    if (s->topo < 0)
+        return fail(MW_EPARSE, "the kinematic topology of this branched model is not compiled into this "
+                               "build (supported: serial chains of 1..9 dofs and the Panda tree)");
     s->pid.assign(s->model.dofs(), kDefaultPid);
     s->model_name = (name && *name) ? name : s->model.name;
     s->loaded = true;
@@ -822,18 +593,17 @@ constexpr float kExactPgsTol = 1e-6f;
 // damping set after mw_initialize).
 static int alloc_wave_buffers(mw_sim* s) {
     const size_t W = static_cast<size_t>(s->W);
-    MW_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_pid), mw::kMaxBodies * sizeof(mw::PidF)));
-    MW_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_pid), mw::kMaxBodies * sizeof(mw::PidF),
-                         hipHostMallocDefault));
+    MW_HIP(mw::dev_alloc(s->d_pid, mw::kMaxBodies * sizeof(mw::PidF)));
+    MW_HIP(mw::pin_alloc(s->h_pid, mw::kMaxBodies * sizeof(mw::PidF)));
     // [0] dropped rows (int32, drained into overflow_seen), [2..3] unconverged
     // exact-LCP world-steps (uint64)
-    MW_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_overflow), 4 * sizeof(int)));
-    MW_HIP(hipMemsetAsync(s->d_overflow, 0, 4 * sizeof(int), s->stream));
-    MW_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_overflow), 2 * sizeof(int), hipHostMallocDefault));
+    MW_HIP(mw::dev_alloc(s->d_overflow, 4 * sizeof(int)));
+    MW_HIP(hipMemsetAsync(s->d_overflow.get(), 0, 4 * sizeof(int), s->stream));
+    MW_HIP(mw::pin_alloc(s->h_overflow, 2 * sizeof(int)));
     s->h_overflow[0] = s->h_overflow[1] = 0;
     const size_t wb = static_cast<size_t>(mw::kWaveWarmWordsHost) * W * sizeof(float);
-    MW_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_warm), wb));
-    MW_HIP(hipMemsetAsync(s->d_warm, 0, wb, s->stream));
+    MW_HIP(mw::dev_alloc(s->d_warm, wb));
+    MW_HIP(hipMemsetAsync(s->d_warm.get(), 0, wb, s->stream));
     return MW_OK;
 }
 
@@ -844,7 +614,7 @@ int mw_constraint_overflow(const mw_sim* s, int64_t* rows) {
     *rows = 0;
     if (!s->d_overflow) return MW_OK;
     int v = 0;
-    MW_HIP(hipMemcpyAsync(&v, s->d_overflow, sizeof(int), hipMemcpyDeviceToHost, s->stream));
+    MW_HIP(hipMemcpyAsync(&v, s->d_overflow.get(), sizeof(int), hipMemcpyDeviceToHost, s->stream));
     MW_HIP(hipStreamSynchronize(s->stream));
     *rows = v;
     return MW_OK;
@@ -857,7 +627,7 @@ int mw_lcp_unconverged(const mw_sim* s, int64_t* worlds) {
     *worlds = 0;
     if (!s->d_overflow) return MW_OK;
     uint64_t v = 0;
-    MW_HIP(hipMemcpyAsync(&v, s->d_overflow + 2, sizeof(v), hipMemcpyDeviceToHost, s->stream));
+    MW_HIP(hipMemcpyAsync(&v, s->d_overflow.get() + 2, sizeof(v), hipMemcpyDeviceToHost, s->stream));
     MW_HIP(hipStreamSynchronize(s->stream));
     *worlds = static_cast<int64_t>(v);
     return MW_OK;
@@ -887,74 +657,57 @@ int mw_initialize(mw_sim* s) {
     if (!s->loaded) return fail(MW_ESTATE, "no model loaded");
     MW_HIP(hipSetDevice(s->cfg.device));
     if (!s->stream_set) {
-        MW_HIP(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-        s->own_stream = true;
+        MW_HIP(mw::stream_create(s->own_stream, hipStreamNonBlocking));
+        s->stream = s->own_stream.get();
         s->stream_set = true;
     }
     s->n = s->model.dofs();
     {
         // divergence flags [W] (rounded to 8 bytes) + the uint64 count
         const size_t rw = (static_cast<size_t>(s->W) + 7) & ~size_t{7};
-        MW_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_health), rw + 8));
-        MW_HIP(hipMemsetAsync(s->d_health, 0, rw + 8, s->stream));
-        MW_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_ndiv), sizeof(uint64_t), hipHostMallocDefault));
+        MW_HIP(mw::dev_alloc(s->d_health, rw + 8));
+        MW_HIP(hipMemsetAsync(s->d_health.get(), 0, rw + 8, s->stream));
+        MW_HIP(mw::pin_alloc(s->h_ndiv, sizeof(uint64_t)));
         *s->h_ndiv = 0;
-        s->dev.div = s->fdev.div = s->d_health;
-        s->dev.ndiv = s->fdev.ndiv = reinterpret_cast<unsigned long long*>(s->d_health + rw);
+        s->dev.div = s->fdev.div = s->d_health.get();
+        s->dev.ndiv = s->fdev.ndiv = reinterpret_cast<unsigned long long*>(s->d_health.get() + rw);
     }
     if (s->fbase()) {
         const size_t W = static_cast<size_t>(s->W);
         const size_t ns = static_cast<size_t>(s->n_slots);
         const size_t nf = (13 + 7 + 6 + 7 * ns) * W;
-        MW_HIP(hipMalloc(&s->d_fblock, nf * sizeof(float) + W * (1 + sizeof(uint32_t)) + 64));
+        MW_HIP(mw::dev_alloc(s->d_fblock, nf * sizeof(float) + W * (1 + sizeof(uint32_t)) + 64));
         if (s->float_tree) {
-            MW_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_float), sizeof(mw::FloatF)));
+            MW_HIP(mw::dev_alloc(s->d_float, sizeof(mw::FloatF)));
             if (s->wave) {
                 if (int rc = alloc_wave_buffers(s)) return rc;
             } else {
                 const size_t words = static_cast<size_t>(mw::float_workspace_words(s->n, s->n_slots));
-                MW_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_ws), words * W * sizeof(float)));
+                MW_HIP(mw::dev_alloc(s->d_ws, words * W * sizeof(float)));
             }
         } else {
-            MW_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_free), sizeof(mw::FreeF)));
+            MW_HIP(mw::dev_alloc(s->d_free, sizeof(mw::FreeF)));
         }
-        float* f = static_cast<float*>(s->d_fblock);
+        float* f = static_cast<float*>(s->d_fblock.get());
         s->fdev.base = f;
         s->fdev.rpose = f + 13 * W;
         s->fdev.rvel = f + 20 * W;
         s->fdev.cdata = f + 26 * W;
         s->fdev.cmask = reinterpret_cast<uint32_t*>(f + nf);
         s->fdev.rflag = reinterpret_cast<uint8_t*>(s->fdev.cmask + W);
-        s->fdev.warm = s->d_warm;
-        MW_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_base), 13 * W * sizeof(float), hipHostMallocDefault));
-        MW_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_cdata), 7 * ns * W * sizeof(float),
-                             hipHostMallocDefault));
-        MW_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_cmask), W * sizeof(uint32_t), hipHostMallocDefault));
-        std::memset(s->h_cmask, 0, W * sizeof(uint32_t));
+        s->fdev.warm = s->d_warm.get();
+        MW_HIP(mw::pin_alloc(s->h_base, 13 * W * sizeof(float)));
+        MW_HIP(mw::pin_alloc(s->h_cdata, 7 * ns * W * sizeof(float)));
+        MW_HIP(mw::pin_alloc(s->h_cmask, W * sizeof(uint32_t)));
+        std::memset(s->h_cmask.get(), 0, W * sizeof(uint32_t));
         // the insertion pose; at rest
-        const auto& R = s->model.base_R;
-        double qw, qx, qy, qz;
-        {
-            const double tr = R[0] + R[4] + R[8];
-            if (tr > 0) {
-                const double k = 0.5 / std::sqrt(tr + 1.0);
-                qw = 0.25 / k; qx = (R[7] - R[5]) * k; qy = (R[2] - R[6]) * k; qz = (R[3] - R[1]) * k;
-            } else if (R[0] > R[4] && R[0] > R[8]) {
-                const double k = 2.0 * std::sqrt(1.0 + R[0] - R[4] - R[8]);
-                qw = (R[7] - R[5]) / k; qx = 0.25 * k; qy = (R[1] + R[3]) / k; qz = (R[2] + R[6]) / k;
-            } else if (R[4] > R[8]) {
-                const double k = 2.0 * std::sqrt(1.0 + R[4] - R[0] - R[8]);
-                qw = (R[2] - R[6]) / k; qx = (R[1] + R[3]) / k; qy = 0.25 * k; qz = (R[5] + R[7]) / k;
-            } else {
-                const double k = 2.0 * std::sqrt(1.0 + R[8] - R[0] - R[4]);
-                qw = (R[3] - R[1]) / k; qx = (R[2] + R[6]) / k; qy = (R[5] + R[7]) / k; qz = 0.25 * k;
-            }
-        }
-        const double init[13] = {s->model.base_p[0], s->model.base_p[1], s->model.base_p[2], qw, qx, qy, qz,
+        double q[4];
+        mw::quat_of(s->model.base_R, q);
+        const double init[13] = {s->model.base_p[0], s->model.base_p[1], s->model.base_p[2], q[0], q[1], q[2], q[3],
                                  0, 0, 0, 0, 0, 0};
         for (int f2 = 0; f2 < 13; ++f2)
             for (size_t w = 0; w < W; ++w) s->h_base[f2 * W + w] = static_cast<float>(init[f2]);
-        MW_HIP(hipMemcpyAsync(s->fdev.base, s->h_base, 13 * W * sizeof(float), hipMemcpyHostToDevice, s->stream));
+        MW_HIP(hipMemcpyAsync(s->fdev.base, s->h_base.get(), 13 * W * sizeof(float), hipMemcpyHostToDevice, s->stream));
         MW_HIP(hipMemsetAsync(s->fdev.cmask, 0, W * (1 + sizeof(uint32_t)), s->stream));
         s->h_rpose.assign(7 * W, 0.f);
         s->h_rvel.assign(6 * W, 0.f);
@@ -975,18 +728,17 @@ int mw_initialize(mw_sim* s) {
     // (a joint-less floating body on the wave kernel has no joint arrays:
     // every allocation keeps a minimal size)
     auto sz = [](size_t b) { return std::max<size_t>(b, 64); };
-    MW_HIP(hipMalloc(&s->d_block, sz(s->block_bytes)));
-    MW_HIP(hipMalloc(&s->d_params, sizeof(mw::ChainF)));
-    MW_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_aux), sz(5 * s->nw * sizeof(float))));
-    MW_HIP(hipMemsetAsync(s->d_aux, 0, 5 * s->nw * sizeof(float), s->stream));
-    MW_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_ptgt), sz(s->nw * sizeof(float)), hipHostMallocDefault));
-    std::memset(s->h_ptgt, 0, s->nw * sizeof(float));
-    MW_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_block), sz(s->block_bytes), hipHostMallocDefault));
-    std::memset(s->h_block, 0, s->block_bytes);
-    MW_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_stage), sz(s->cmd_bytes + s->nw * sizeof(float)),
-                         hipHostMallocDefault));
-    MW_HIP(hipEventCreateWithFlags(&s->stage_ev, hipEventDisableTiming));
-    float* base = reinterpret_cast<float*>(s->d_block);
+    MW_HIP(mw::dev_alloc(s->d_block, sz(s->block_bytes)));
+    MW_HIP(mw::dev_alloc(s->d_params, sizeof(mw::ChainF)));
+    MW_HIP(mw::dev_alloc(s->d_aux, sz(5 * s->nw * sizeof(float))));
+    MW_HIP(hipMemsetAsync(s->d_aux.get(), 0, 5 * s->nw * sizeof(float), s->stream));
+    MW_HIP(mw::pin_alloc(s->h_ptgt, sz(s->nw * sizeof(float))));
+    std::memset(s->h_ptgt.get(), 0, s->nw * sizeof(float));
+    MW_HIP(mw::pin_alloc(s->h_block, sz(s->block_bytes)));
+    std::memset(s->h_block.get(), 0, s->block_bytes);
+    MW_HIP(mw::pin_alloc(s->h_stage, sz(s->cmd_bytes + s->nw * sizeof(float))));
+    MW_HIP(mw::event_create(s->stage_ev, hipEventDisableTiming));
+    float* base = reinterpret_cast<float*>(s->d_block.get());
     s->dev.q = base;
     s->dev.qd = base + s->nw;
     s->dev.qdd = base + 2 * s->nw;
@@ -996,18 +748,18 @@ int mw_initialize(mw_sim* s) {
     s->dev.rqd = base + 6 * s->nw;
     s->dev.act = reinterpret_cast<uint8_t*>(base + 7 * s->nw);
     s->dev.rflag = s->dev.act + s->nw;
-    s->dev.ptgt = s->d_aux;
-    s->dev.pid_e = s->d_aux + s->nw;
-    s->dev.pid_i = s->d_aux + 2 * s->nw;
-    s->dev.pid_u = s->d_aux + 3 * s->nw;
-    s->dev.qlo = s->d_aux + 4 * s->nw;
+    s->dev.ptgt = s->d_aux.get();
+    s->dev.pid_e = s->d_aux.get() + s->nw;
+    s->dev.pid_i = s->d_aux.get() + 2 * s->nw;
+    s->dev.pid_u = s->d_aux.get() + 3 * s->nw;
+    s->dev.qlo = s->d_aux.get() + 4 * s->nw;
     s->mode.assign(s->nw, MW_MODE_IDLE);
     s->ptgt.assign(s->nw, 0.0);
     s->cmd64.assign(s->nw, 0.0);
     s->initialized = true;
     int rc = upload_params(s);
     if (rc) return rc;
-    MW_HIP(hipMemcpyAsync(s->d_block, s->h_block, s->block_bytes, hipMemcpyHostToDevice, s->stream));
+    MW_HIP(hipMemcpyAsync(s->d_block.get(), s->h_block.get(), s->block_bytes, hipMemcpyHostToDevice, s->stream));
     MW_HIP(hipStreamSynchronize(s->stream));
     s->cmd_dirty = false;
     return MW_OK;
@@ -1018,9 +770,8 @@ int mw_initialized(const mw_sim* s) { return (s && s->initialized) ? 1 : 0; }
 int mw_set_stream(mw_sim* s, void* stream) {
     if (!s) return fail(MW_EINVAL, "null simulator handle");
     if (s->initialized) MW_HIP(hipStreamSynchronize(s->stream));
-    if (s->own_stream && s->stream) (void)hipStreamDestroy(s->stream);
+    s->own_stream.reset();
     s->stream = static_cast<hipStream_t>(stream);
-    s->own_stream = false;
     s->stream_set = true;
     return MW_OK;
 }
@@ -1040,7 +791,6 @@ static int report_divergence(mw_sim* s) {
 static int upload_base_resets(mw_sim* s) {
     const size_t W = static_cast<size_t>(s->W);
     if (s->free_dirty) {
-        // pending base resets: one H2D copy of [rpose | rvel] and the flags
         MW_HIP(hipMemcpyAsync(s->fdev.rpose, s->h_rpose.data(), 7 * W * sizeof(float), hipMemcpyHostToDevice,
                               s->stream));
         MW_HIP(hipMemcpyAsync(s->fdev.rvel, s->h_rvel.data(), 6 * W * sizeof(float), hipMemcpyHostToDevice,
@@ -1056,10 +806,10 @@ static int upload_base_resets(mw_sim* s) {
 // contacts + base of the last run -> host mirrors (queued on the stream)
 static int read_base(mw_sim* s, int paused) {
     const size_t W = static_cast<size_t>(s->W);
-    MW_HIP(hipMemcpyAsync(s->h_base, s->fdev.base, 13 * W * sizeof(float), hipMemcpyDeviceToHost, s->stream));
+    MW_HIP(hipMemcpyAsync(s->h_base.get(), s->fdev.base, 13 * W * sizeof(float), hipMemcpyDeviceToHost, s->stream));
     if (s->contacts && !paused) {
-        MW_HIP(hipMemcpyAsync(s->h_cmask, s->fdev.cmask, W * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        MW_HIP(hipMemcpyAsync(s->h_cdata, s->fdev.cdata, 7 * static_cast<size_t>(s->n_slots) * W * sizeof(float),
+        MW_HIP(hipMemcpyAsync(s->h_cmask.get(), s->fdev.cmask, W * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
+        MW_HIP(hipMemcpyAsync(s->h_cdata.get(), s->fdev.cdata, 7 * static_cast<size_t>(s->n_slots) * W * sizeof(float),
                               hipMemcpyDeviceToHost, s->stream));
     }
     return MW_OK;
@@ -1077,7 +827,7 @@ static int run_free(mw_sim* s, int paused, bool readback = true) {
     a.substeps = paused ? 0 : s->cfg.steps_per_run;
     int mesh = 0;
     for (int k = 0; k < s->h_free.n_shapes; ++k) mesh |= s->h_free.shape_type[k] == mw::Shape::Mesh;
-    MW_HIP(mw::launch_free_run(s->d_free, s->fdev, s->W, a, s->contacts ? 1 : 0, mesh, s->stream));
+    MW_HIP(mw::launch_free_run(s->d_free.get(), s->fdev, s->W, a, s->contacts ? 1 : 0, mesh, s->stream));
     if (!paused) {
         s->iterations += s->cfg.steps_per_run;
         s->stepped = true;
@@ -1088,7 +838,7 @@ static int run_free(mw_sim* s, int paused, bool readback = true) {
         return MW_OK;
     }
     if ((rc = read_base(s, paused))) return rc;
-    MW_HIP(hipMemcpyAsync(s->h_ndiv, s->dev.ndiv, sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+    MW_HIP(hipMemcpyAsync(s->h_ndiv.get(), s->dev.ndiv, sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
     MW_HIP(hipStreamSynchronize(s->stream));
     s->contacts_stale = false;
     return report_divergence(s);
@@ -1110,17 +860,19 @@ static int stage_wrenches(mw_sim* s, int64_t it0, int& chunk) {
     if (cap != hipStreamCaptureStatusNone)
         return fail(MW_ESTATE, "world wrenches cannot be captured into a graph: run them outside the capture");
     MW_HIP(hipStreamSynchronize(s->stream));  // the staging buffer of the previous launch
-    std::fill(s->h_ext, s->h_ext + 6 * st, 0.f);
+    std::fill(s->h_ext.get(), s->h_ext.get() + 6 * st, 0.f);
     for (int sl = 0; sl < mw::kSimWrenchSlots; ++sl)
         for (size_t nw = 0; nw < st; ++nw) {
             if (s->h_wl[sl * st + nw] < it0 + chunk) continue;
             for (int e = 0; e < 6; ++e) s->h_ext[e * st + nw] += s->h_wr[(static_cast<size_t>(sl) * 6 + e) * st + nw];
         }
-    MW_HIP(hipMemcpyAsync(s->d_ext, s->h_ext, 6 * st * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    MW_HIP(hipMemcpyAsync(s->d_ext.get(), s->h_ext.get(), 6 * st * sizeof(float), hipMemcpyHostToDevice, s->stream));
     return MW_OK;
 }
 
-static int run_impl(mw_sim* s, int paused, bool readback) {
+}  // extern "C"
+
+int run_impl(mw_sim* s, int paused, bool readback) {
     int rc = check_sim(s);
     if (rc) return rc;
     // a device-resident run never needs the host mirror (and must not
@@ -1140,22 +892,22 @@ static int run_impl(mw_sim* s, int paused, bool readback) {
             return fail(MW_ESTATE, "pending joint commands, resets or targets cannot be captured into a graph: "
                                    "apply them with a run before capturing");
         if (s->stage_pending) {
-            MW_HIP(hipEventSynchronize(s->stage_ev));  // the previous copy out of the stage is done
+            MW_HIP(hipEventSynchronize(s->stage_ev.get()));  // the previous copy out of the stage is done
             s->stage_pending = false;
         }
         if (s->cmd_dirty) {
-            std::memcpy(s->h_stage, s->h_block + s->cmd_off, s->cmd_bytes);
-            MW_HIP(hipMemcpyAsync(static_cast<uint8_t*>(s->d_block) + s->cmd_off, s->h_stage, s->cmd_bytes,
+            std::memcpy(s->h_stage.get(), s->h_block.get() + s->cmd_off, s->cmd_bytes);
+            MW_HIP(hipMemcpyAsync(static_cast<uint8_t*>(s->d_block.get()) + s->cmd_off, s->h_stage.get(), s->cmd_bytes,
                                   hipMemcpyHostToDevice, s->stream));
             s->cmd_dirty = false;
         }
         if (s->ptgt_dirty) {
-            std::memcpy(s->h_stage + s->cmd_bytes, s->h_ptgt, s->nw * sizeof(float));
-            MW_HIP(hipMemcpyAsync(s->d_aux, s->h_stage + s->cmd_bytes, s->nw * sizeof(float),
+            std::memcpy(s->h_stage.get() + s->cmd_bytes, s->h_ptgt.get(), s->nw * sizeof(float));
+            MW_HIP(hipMemcpyAsync(s->d_aux.get(), s->h_stage.get() + s->cmd_bytes, s->nw * sizeof(float),
                                   hipMemcpyHostToDevice, s->stream));
             s->ptgt_dirty = false;
         }
-        MW_HIP(hipEventRecord(s->stage_ev, s->stream));
+        MW_HIP(hipEventRecord(s->stage_ev.get(), s->stream));
         s->stage_pending = true;
     }
     const mw::PidSet pid = pid_set(s);
@@ -1170,7 +922,8 @@ static int run_impl(mw_sim* s, int paused, bool readback) {
             s->h_pid[d] = {to_f32(g[0]), to_f32(g[1]), to_f32(g[2]), to_f32(g[7]), to_f32(g[6]),
                            to_f32(g[4]), to_f32(g[3]), to_f32(g[5])};
         }
-        MW_HIP(hipMemcpyAsync(s->d_pid, s->h_pid, s->n * sizeof(mw::PidF), hipMemcpyHostToDevice, s->stream));
+        MW_HIP(hipMemcpyAsync(s->d_pid.get(), s->h_pid.get(), s->n * sizeof(mw::PidF), hipMemcpyHostToDevice,
+                              s->stream));
     }
     mw::RunArgs a{};
     a.dt = static_cast<float>(s->cfg.step_size);
@@ -1209,23 +962,25 @@ static int run_impl(mw_sim* s, int paused, bool readback) {
             }
         }
         if (s->wave)
-            MW_HIP(mw::launch_wave_run(s->d_params, s->n, s->wave_depth, needs_cons(s), s->d_float, s->dev, s->fdev, s->d_pid, s->W,
-                                       a, s->contacts ? 1 : 0, s->d_overflow, s->stream));
+            MW_HIP(mw::launch_wave_run(s->d_params.get(), s->n, s->wave_depth, needs_cons(s), s->d_float.get(), s->dev,
+                                       s->fdev, s->d_pid.get(), s->W, a, s->contacts ? 1 : 0, s->d_overflow.get(),
+                                       s->stream));
         else if (s->float_tree)
-            MW_HIP(mw::launch_float_run(s->d_params, s->n, s->topo, needs_cons(s), s->d_float, s->dev, s->fdev, pid,
-                                        s->d_ws, s->W, a, s->contacts ? 1 : 0, s->stream));
+            MW_HIP(mw::launch_float_run(s->d_params.get(), s->n, s->topo, needs_cons(s), s->d_float.get(), s->dev,
+                                        s->fdev, pid, s->d_ws.get(), s->W, a, s->contacts ? 1 : 0, s->stream));
         else
-            MW_HIP(mw::launch_scenario_run(s->d_params, s->n, s->topo, needs_cons(s), needs_dual(s), baked_id(s),
+            MW_HIP(mw::launch_scenario_run(s->d_params.get(), s->n, s->topo, needs_cons(s), needs_dual(s), baked_id(s),
                                            s->dev, pid, s->W, a, s->stream));
         a.first = 0;
         done += chunk;
     } while (!paused && done < spr);
     if (readback) {
-        MW_HIP(hipMemcpyAsync(s->h_block, s->d_block, s->state_bytes, hipMemcpyDeviceToHost, s->stream));
+        MW_HIP(hipMemcpyAsync(s->h_block.get(), s->d_block.get(), s->state_bytes, hipMemcpyDeviceToHost, s->stream));
         if (s->float_tree && (rc = read_base(s, paused))) return rc;
         if (s->h_overflow)
-            MW_HIP(hipMemcpyAsync(s->h_overflow, s->d_overflow, 2 * sizeof(int), hipMemcpyDeviceToHost, s->stream));
-        MW_HIP(hipMemcpyAsync(s->h_ndiv, s->dev.ndiv, sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
+            MW_HIP(hipMemcpyAsync(s->h_overflow.get(), s->d_overflow.get(), 2 * sizeof(int), hipMemcpyDeviceToHost,
+                                  s->stream));
+        MW_HIP(hipMemcpyAsync(s->h_ndiv.get(), s->dev.ndiv, sizeof(uint64_t), hipMemcpyDeviceToHost, s->stream));
         MW_HIP(hipStreamSynchronize(s->stream));
         s->contacts_stale = false;
     } else {
@@ -1240,17 +995,19 @@ static int run_impl(mw_sim* s, int paused, bool readback) {
         s->iterations += s->cfg.steps_per_run;
         s->stepped = true;
     }
-    if (readback && s->h_overflow && *s->h_overflow > s->overflow_seen) {
+    if (readback && s->h_overflow && s->h_overflow[0] > s->overflow_seen) {
         // DART keeps every contact: a run that dropped constraint rows fails
         // loudly (the state has advanced without them)
-        const int64_t d = *s->h_overflow - s->overflow_seen;
-        s->overflow_seen = *s->h_overflow;
+        const int64_t d = s->h_overflow[0] - s->overflow_seen;
+        s->overflow_seen = s->h_overflow[0];
         return fail(MW_ECAPACITY, "this run dropped " + std::to_string(d) +
                                       " constraint rows: a world exceeded the per-step capacity of the "
                                       "world-per-wavefront kernel (64 rows)");
     }
     return readback ? report_divergence(s) : MW_OK;
 }
+
+extern "C" {
 
 int mw_run(mw_sim* s, int paused) { return run_impl(s, paused, true); }
 
@@ -1354,10 +1111,10 @@ int mw_set_joint_param(mw_sim* s, int32_t dof, int32_t which, double value) {
             if (!s->wave_depth_ok)
                 return fail(MW_EPARSE, "joint damping on this floating-base model needs the world-per-wavefront "
                                        "kernel, whose depth limit the tree exceeds");
-            if (s->initialized && !s->d_pid) {
+            if (s->initialized && !s->d_warm) {  // alloc_wave_buffers' last: a failed attempt is repeated whole
                 int rc = alloc_wave_buffers(s);
                 if (rc) return rc;
-                s->fdev.warm = s->d_warm;
+                s->fdev.warm = s->d_warm.get();
                 s->pid_dirty = true;
             }
             s->wave = true;
@@ -1700,28 +1457,14 @@ int mw_is_floating(const mw_sim* s, int32_t* floating) {
     return MW_OK;
 }
 
-static float* base_at(const mw_sim* s, int f, int w) { return s->h_base + static_cast<size_t>(f) * s->W + w; }
+static float* base_at(const mw_sim* s, int f, int w) { return s->h_base.get() + static_cast<size_t>(f) * s->W + w; }
 
 // the base of a fixed-base model is the model frame, at rest (Model::basePosition
 // reads the model's Pose component, Model.cpp:976-994)
 static int fixed_base_pose(const mw_sim* s, int32_t w0, int32_t nw, double* out, bool velocity) {
     if (!out || w0 < 0 || nw < 0 || w0 + nw > s->W) return fail(MW_EINVAL, "bad world range or null output");
-    const auto& R = s->model.base_R;
-    const double tr = R[0] + R[4] + R[8];
     double q[4];
-    if (tr > 0) {
-        const double k = 0.5 / std::sqrt(tr + 1.0);
-        q[0] = 0.25 / k; q[1] = (R[7] - R[5]) * k; q[2] = (R[2] - R[6]) * k; q[3] = (R[3] - R[1]) * k;
-    } else if (R[0] > R[4] && R[0] > R[8]) {
-        const double k = 2.0 * std::sqrt(1.0 + R[0] - R[4] - R[8]);
-        q[0] = (R[7] - R[5]) / k; q[1] = 0.25 * k; q[2] = (R[1] + R[3]) / k; q[3] = (R[2] + R[6]) / k;
-    } else if (R[4] > R[8]) {
-        const double k = 2.0 * std::sqrt(1.0 + R[4] - R[0] - R[8]);
-        q[0] = (R[2] - R[6]) / k; q[1] = (R[1] + R[3]) / k; q[2] = 0.25 * k; q[3] = (R[5] + R[7]) / k;
-    } else {
-        const double k = 2.0 * std::sqrt(1.0 + R[8] - R[0] - R[4]);
-        q[0] = (R[3] - R[1]) / k; q[1] = (R[2] + R[6]) / k; q[2] = (R[5] + R[7]) / k; q[3] = 0.25 * k;
-    }
+    mw::quat_of(s->model.base_R, q);
     for (int32_t k = 0; k < nw; ++k) {
         if (velocity) {
             for (int f = 0; f < 6; ++f) out[6 * k + f] = 0.0;
@@ -1815,7 +1558,7 @@ int mw_set_pgs_options(mw_sim* s, double tol, int32_t warm_start) {
                                "bases / generic fixed trees); this model runs on another kernel");
     if (warm && !s->pgs_warm && s->d_warm) {
         // a fresh warm start: no stale impulses from before the option was off
-        MW_HIP(hipMemsetAsync(s->d_warm, 0, static_cast<size_t>(mw::kWaveWarmWordsHost) * s->W * sizeof(float),
+        MW_HIP(hipMemsetAsync(s->d_warm.get(), 0, static_cast<size_t>(mw::kWaveWarmWordsHost) * s->W * sizeof(float),
                               s->stream));
     }
     s->pgs_tol = tol;
@@ -1842,12 +1585,12 @@ int mw_apply_link_wrench(mw_sim* s, int32_t link, int32_t w0, int32_t nw, const 
     if (!(duration >= 0.0)) return fail(MW_EINVAL, "the wrench duration must be >= 0");
     const int nn = s->n + 1;
     const size_t W = static_cast<size_t>(s->W);
-    if (!s->d_ext) {
+    if (!s->h_ext) {  // the last of the two allocations: a failed attempt is repeated whole
         s->h_wr.assign(static_cast<size_t>(mw::kSimWrenchSlots) * 6 * nn * W, 0.f);
         s->h_wl.assign(static_cast<size_t>(mw::kSimWrenchSlots) * nn * W, -1);
-        MW_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_ext), 6 * nn * W * sizeof(float)));
-        MW_HIP(hipHostMalloc(reinterpret_cast<void**>(&s->h_ext), 6 * nn * W * sizeof(float), hipHostMallocDefault));
-        s->fdev.wrench = s->d_ext;
+        MW_HIP(mw::dev_alloc(s->d_ext, 6 * nn * W * sizeof(float)));
+        MW_HIP(mw::pin_alloc(s->h_ext, 6 * nn * W * sizeof(float)));
+        s->fdev.wrench = s->d_ext.get();
         s->fdev.wnodes = nn;
     }
     const int node = link + 1;
@@ -1925,7 +1668,7 @@ int mw_enable_contacts(mw_sim* s, int32_t enable) {
     if (!s) return fail(MW_EINVAL, "null simulator handle");
     // Model::enableContacts (Model.cpp:686-700)
     s->contacts = enable != 0;
-    if (!s->contacts && s->h_cmask) std::memset(s->h_cmask, 0, static_cast<size_t>(s->W) * sizeof(uint32_t));
+    if (!s->contacts && s->h_cmask) std::memset(s->h_cmask.get(), 0, static_cast<size_t>(s->W) * sizeof(uint32_t));
     return MW_OK;
 }
 
@@ -1945,8 +1688,9 @@ int mw_get_contacts(const mw_sim* s, int32_t w, double* out, int32_t cap, int32_
     if (s->contacts_stale) {
         mw_sim* m = const_cast<mw_sim*>(s);
         const size_t Wc = static_cast<size_t>(s->W);
-        MW_HIP(hipMemcpyAsync(m->h_cmask, s->fdev.cmask, Wc * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
-        MW_HIP(hipMemcpyAsync(m->h_cdata, s->fdev.cdata, 7 * static_cast<size_t>(s->n_slots) * Wc * sizeof(float),
+        MW_HIP(hipMemcpyAsync(m->h_cmask.get(), s->fdev.cmask, Wc * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                              s->stream));
+        MW_HIP(hipMemcpyAsync(m->h_cdata.get(), s->fdev.cdata, 7 * static_cast<size_t>(s->n_slots) * Wc * sizeof(float),
                               hipMemcpyDeviceToHost, s->stream));
         MW_HIP(hipStreamSynchronize(s->stream));
         m->contacts_stale = false;
@@ -1959,7 +1703,7 @@ int mw_get_contacts(const mw_sim* s, int32_t w, double* out, int32_t cap, int32_
     for (int slot = 0; slot < s->n_slots; ++slot) {
         if (!((mask >> slot) & 1u)) continue;
         if (k < cap) {
-            const float* c = s->h_cdata + static_cast<size_t>(slot) * 7 * W + w;
+            const float* c = s->h_cdata.get() + static_cast<size_t>(slot) * 7 * W + w;
             double* o = out + 10 * k;
             o[0] = c[0]; o[1] = c[W]; o[2] = c[2 * W];
             o[3] = 0.0; o[4] = 0.0; o[5] = 1.0;
@@ -2004,7 +1748,8 @@ int mw_device_ptr(mw_sim* s, const char* field, void** dptr, int64_t* stride) {
         // the caller drives the targets on the device from now on
         if ((rc = pull_ptgt(s))) return rc;
         if (s->ptgt_dirty) {
-            MW_HIP(hipMemcpyAsync(s->d_aux, s->h_ptgt, s->nw * sizeof(float), hipMemcpyHostToDevice, s->stream));
+            MW_HIP(hipMemcpyAsync(s->d_aux.get(), s->h_ptgt.get(), s->nw * sizeof(float), hipMemcpyHostToDevice,
+                                  s->stream));
             s->ptgt_dirty = false;
         }
         *dptr = s->dev.ptgt;
@@ -2111,323 +1856,6 @@ int mw_copy_state(mw_sim* s, float* q, float* qd, int to_sim) {
         MW_HIP(hipMemcpyAsync(q, s->dev.q, bytes, hipMemcpyDeviceToDevice, s->stream));
         MW_HIP(hipMemcpyAsync(qd, s->dev.qd, bytes, hipMemcpyDeviceToDevice, s->stream));
     }
-    return MW_OK;
-}
-
-// ------------------------------------------------------------- VecEnv ----
-
-int mw_vecenv_create(mw_sim* s, const mw_task_config* cfg, mw_vecenv** out) {
-    int rc = check_sim(s);
-    if (rc) return rc;
-    if (!cfg || !out) return fail(MW_EINVAL, "null argument");
-    *out = nullptr;
-    const int n = s->n;
-    // the batched env kernels step fixed-base chains only: a floating model
-    // with a matching dof count would have its base and contacts ignored
-    if (s->floating) return fail(MW_EINVAL, "the batched env tasks need a fixed-base model");
-    // ... and a compiled chain topology: a generic fixed tree (wave kernel) or
-    // a branched 1-2 dof model would be stepped as a serial chain
-    if (s->fixed_tree || s->topo < 0)
-        return fail(MW_EINVAL, "the batched env tasks need a serial-chain model (or the shipped Panda tree)");
-    const bool cart = cfg->kind >= MW_TASK_CARTPOLE_DISCRETE && cfg->kind <= MW_TASK_CARTPOLE_CONTINUOUS_SWINGUP;
-    const bool pidtask = cfg->kind == MW_TASK_PANDA_POSITION_TRACKING;
-    if (cart && n != 2) return fail(MW_EINVAL, "CartPole tasks need the 2-dof cartpole model");
-    if (cfg->kind == MW_TASK_PENDULUM_SWINGUP && n != 1) return fail(MW_EINVAL, "PendulumSwingUp needs the 1-dof pendulum model");
-    if (pidtask && (n != 9 || s->topo != 1))
-        return fail(MW_EINVAL, "PandaPositionTracking needs the 9-dof Panda model");
-    if (pidtask && s->cfg.steps_per_run > 64) return fail(MW_EINVAL, "steps_per_run must be <= 64");
-    if (!cart && !pidtask && cfg->kind != MW_TASK_PENDULUM_SWINGUP) return fail(MW_EINVAL, "unknown task kind");
-    auto e = std::make_unique<mw_vecenv>();
-    e->sim = s;
-    e->cfg = *cfg;
-    mw::TaskF& T = e->task;
-    T.kind = cfg->kind;
-    T.max_steps = cfg->max_episode_steps;
-    T.reward_cart_at_center = cfg->reward_cart_at_center;
-    T.n_obs = (cfg->kind == MW_TASK_PENDULUM_SWINGUP) ? 3 : (pidtask ? 2 * n : 4);
-    T.seed_lo = static_cast<uint32_t>(cfg->seed);
-    T.seed_hi = static_cast<uint32_t>(cfg->seed >> 32);
-    if (cfg->world_offset < 0) return fail(MW_EINVAL, "world_offset must be >= 0");
-    T.world_offset = static_cast<uint32_t>(cfg->world_offset);
-    T.force_mag = 20.0f;  // cartpole_discrete_balancing.py:32
-    const double pi = 3.14159265358979323846;
-    switch (cfg->kind) {
-    case MW_TASK_CARTPOLE_DISCRETE:
-    case MW_TASK_CARTPOLE_CONTINUOUS_BALANCING:
-        T.x_factor = (cfg->kind == MW_TASK_CARTPOLE_DISCRETE) ? 0.9f : 1.0f;
-        T.hi[0] = 2.4f; T.hi[1] = 20.0f;
-        T.hi[2] = static_cast<float>(12.0 * pi / 180.0);
-        T.hi[3] = static_cast<float>(3.0 * 360.0 * pi / 180.0);
-        break;
-    case MW_TASK_CARTPOLE_CONTINUOUS_SWINGUP:
-        T.x_factor = 0.8f;
-        T.hi[0] = 2.4f; T.hi[1] = 20.0f;
-        T.hi[2] = static_cast<float>(5.0 * 360.0 * pi / 180.0);
-        T.hi[3] = static_cast<float>(3.0 * 360.0 * pi / 180.0);
-        break;
-    case MW_TASK_PENDULUM_SWINGUP:
-        T.x_factor = 0.f;
-        T.hi[0] = 1.f; T.hi[1] = 1.f; T.hi[2] = 10.f; T.hi[3] = 0.f;
-        break;
-    case MW_TASK_PANDA_POSITION_TRACKING: {
-        // the Panda wrapper's initial configuration (models/panda.py:41-44) with
-        // joints 1 and 6 at mid-range as test_pid_controllers.py:49-59 sets them
-        // (so the config-4 sinusoids stay inside the limits) and the fingers
-        // half open: no joint starts on a position limit
-        const double wrapper[7] = {0.0, -0.785, 0.0, -2.356, 0.0, 1.571, 0.785};
-        for (int d = 0; d < n; ++d) {
-            const mw::ChainBody& b = s->model.bodies[d];
-            double h = (d < 7) ? wrapper[d] : 0.5 * (b.lower + b.upper);
-            if (d == 0 || d == 5) h = 0.5 * (b.lower + b.upper);
-            T.home[d] = static_cast<float>(h);
-        }
-        T.home_noise = 0.05f;
-        // the JointController runs every physics step (period = step size)
-        s->period_ns = s->dt_ns;
-        s->controller = true;
-        break;
-    }
-    }
-    if (cfg->randomize & ~(MW_RAND_MASS | MW_RAND_GRAVITY)) return fail(MW_EINVAL, "unknown randomisation bits");
-    if (cfg->randomize && pidtask) return fail(MW_EINVAL, "randomisation is available for the CartPole / Pendulum tasks");
-    if ((cfg->randomize & MW_RAND_MASS) && !(cfg->mass_high >= cfg->mass_low))
-        return fail(MW_EINVAL, "mass_high must be >= mass_low");
-    if ((cfg->randomize & MW_RAND_GRAVITY) && !(cfg->gravity_std >= 0.f))
-        return fail(MW_EINVAL, "gravity_std must be >= 0");
-    T.randomize = cfg->randomize;
-    T.mass_lo = cfg->mass_low;
-    T.mass_hi = cfg->mass_high;
-    T.g_mean = cfg->gravity_mean;
-    T.g_std = cfg->gravity_std;
-    {
-        // the world z axis in the base frame: R_base^T e_z
-        const auto& R = s->model.base_R;
-        for (int k = 0; k < 3; ++k) T.gdir[k] = static_cast<float>(R[6 + k]);
-    }
-    MW_HIP(hipSetDevice(s->cfg.device));
-    if (cfg->randomize) {
-        const size_t bytes = (static_cast<size_t>(n) + 1) * s->W * sizeof(float);
-        MW_HIP(hipMalloc(&e->d_physics, bytes));
-        MW_HIP(hipMemsetAsync(e->d_physics, 0, bytes, s->stream));
-        e->dev.rmass = static_cast<float*>(e->d_physics);
-        e->dev.rgz = e->dev.rmass + static_cast<size_t>(n) * s->W;
-    }
-    MW_HIP(hipMalloc(&e->d_counters, 2 * static_cast<size_t>(s->W) * sizeof(uint32_t)));
-    MW_HIP(hipMemsetAsync(e->d_counters, 0, 2 * static_cast<size_t>(s->W) * sizeof(uint32_t), s->stream));
-    e->dev.episode = static_cast<uint32_t*>(e->d_counters);
-    e->dev.steps = e->dev.episode + s->W;
-    *out = e.release();
-    return MW_OK;
-}
-
-// Batched env of an articulated floating-base model on the wave kernel
-// (float_env_kernel.hip): the env's kernels write the run kernel's command
-// and pending-reset arrays on the device, the run itself is run_impl's.
-int mw_floatenv_create(mw_sim* s, const mw_float_task_config* cfg, mw_vecenv** out) {
-    if (!s || !cfg || !out) return fail(MW_EINVAL, "null argument");
-    *out = nullptr;
-    int rc = check_sim(s);
-    if (rc) return rc;
-    if (!s->floating || !s->float_tree || !s->wave || s->n == 0)
-        return fail(MW_EINVAL, "the floating-base env needs an articulated model on a floating base (joints, "
-                               "mw_is_floating) stepped by the world-per-wavefront kernel (mw_float_kernel == 2)");
-    if (s->env_owned) return fail(MW_ESTATE, "the simulator already has a floating-base env");
-    const int n = s->n;
-    for (int d = 0; d < n; ++d)
-        if (s->model.bodies[d].ball)
-            return fail(MW_EINVAL, "the floating-base env does not take models with ball joints (joint '" +
-                                       s->model.bodies[d].joint_name + "')");
-    if (s->cfg.steps_per_run > 64) return fail(MW_EINVAL, "steps_per_run must be <= 64");
-    if (cfg->action_mode != MW_FLOAT_ACTION_TORQUE && cfg->action_mode != MW_FLOAT_ACTION_POSITION)
-        return fail(MW_EINVAL, "unknown action mode");
-    if (cfg->max_episode_steps < 0) return fail(MW_EINVAL, "max_episode_steps must be >= 0");
-    if (cfg->world_offset < 0) return fail(MW_EINVAL, "world_offset must be >= 0");
-    if (!cfg->home_q) return fail(MW_EINVAL, "home_q is null (one value per dof)");
-    if (cfg->n_contact_links < 0 || cfg->n_contact_links > mw::kMaxContactLinks)
-        return fail(MW_EINVAL, "n_contact_links must be in [0, " + std::to_string(mw::kMaxContactLinks) + "]");
-    if (cfg->n_contact_links > 0 && !cfg->contact_links) return fail(MW_EINVAL, "contact_links is null");
-    for (int j = 0; j < cfg->n_contact_links; ++j)
-        if (cfg->contact_links[j] < -1 || cfg->contact_links[j] >= n)
-            return fail(MW_EINVAL, "contact link " + std::to_string(cfg->contact_links[j]) + " out of range [-1, " +
-                                       std::to_string(n) + ")");
-    {
-        const float* hb = cfg->home_base;
-        if (!(hb[3] * hb[3] + hb[4] * hb[4] + hb[5] * hb[5] + hb[6] * hb[6] > 0.f))
-            return fail(MW_EINVAL, "the home_base orientation quaternion is zero");
-    }
-    if (!(cfg->joint_noise >= 0.f)) return fail(MW_EINVAL, "joint_noise must be >= 0");
-    auto e = std::make_unique<mw_vecenv>();
-    e->sim = s;
-    e->floatenv = true;
-    mw::FloatTaskF& T = e->ftask;
-    T.action_mode = cfg->action_mode;
-    T.max_steps = cfg->max_episode_steps;
-    T.n_links = cfg->n_contact_links;
-    T.n_obs = 13 + 2 * n + cfg->n_contact_links;
-    T.seed_lo = static_cast<uint32_t>(cfg->seed);
-    T.seed_hi = static_cast<uint32_t>(cfg->seed >> 32);
-    T.world_offset = static_cast<uint32_t>(cfg->world_offset);
-    T.z_min = cfg->z_min;
-    T.cos_tilt_max = cfg->cos_tilt_max;
-    T.alive_bonus = cfg->alive_bonus;
-    T.w_forward = cfg->w_forward;
-    T.w_action = cfg->w_action;
-    T.w_pose = cfg->w_pose;
-    T.joint_noise = cfg->joint_noise;
-    for (int k = 0; k < 7; ++k) T.home_base[k] = cfg->home_base[k];
-    for (int d = 0; d < n; ++d) T.home_q[d] = cfg->home_q[d];
-    // the contact slots of every link (FloatF::shape_body / shape_slot0 order:
-    // slot_body); the wave kernel's contact mask holds 32 slots
-    for (int j = 0; j < cfg->n_contact_links; ++j)
-        for (int slot = 0; slot < s->n_slots && slot < 32; ++slot)
-            if (s->slot_body[slot] == cfg->contact_links[j]) T.link_slots[j] |= 1u << slot;
-    e->task.n_obs = T.n_obs;  // mw_vecenv_obs_dim
-    MW_HIP(hipSetDevice(s->cfg.device));
-    // every dof in Force or Position mode; Position: the JointController runs
-    // every physics step (period = step size), as the Panda task sets it
-    const bool pos = cfg->action_mode == MW_FLOAT_ACTION_POSITION;
-    if ((rc = mw_set_joint_control_mode(s, 0, s->W, nullptr, 0, pos ? MW_MODE_POSITION : MW_MODE_FORCE))) return rc;
-    if (pos) s->period_ns = s->dt_ns;
-    // flush the modes, targets and gains now: from here on the command block
-    // is written on the device only, and a step must find nothing to stage
-    if ((rc = run_impl(s, 1, false))) return rc;
-    const size_t W = static_cast<size_t>(s->W);
-    MW_HIP(hipMalloc(&e->d_counters, 2 * W * sizeof(uint32_t)));
-    MW_HIP(hipMemsetAsync(e->d_counters, 0, 2 * W * sizeof(uint32_t), s->stream));
-    e->dev.episode = static_cast<uint32_t*>(e->d_counters);
-    e->dev.steps = e->dev.episode + W;
-    MW_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_asq), W * sizeof(float)));
-    MW_HIP(hipMemsetAsync(e->d_asq, 0, W * sizeof(float), s->stream));
-    s->env_owned = true;
-    *out = e.release();
-    return MW_OK;
-}
-
-static int floatenv_reset(mw_vecenv* e, float* obs) {
-    mw_sim* s = e->sim;
-    MW_HIP(mw::launch_float_env_post(s->d_params, e->ftask, s->dev, s->fdev, e->dev, e->d_asq, obs, nullptr, nullptr,
-                                     nullptr, s->n, s->W, 1, s->stream));
-    // a paused run applies the pending resets: the state (and the host
-    // getters) show the reset at once
-    return run_impl(s, 1, false);
-}
-
-static int floatenv_step(mw_vecenv* e, const void* a, float* o, float* r, uint8_t* d, float* to) {
-    mw_sim* s = e->sim;
-    const bool pos = e->ftask.action_mode == MW_FLOAT_ACTION_POSITION;
-    MW_HIP(mw::launch_float_env_action(static_cast<const float*>(a), pos ? s->dev.ptgt : s->dev.cmd, e->d_asq,
-                                       s->dev.div, s->dev.ndiv, s->n, s->W, s->stream));
-    if (pos) s->ptgt_stale = true;  // the host mirror of the targets re-reads the device copy
-    if (int rc = run_impl(s, 0, false)) return rc;
-    MW_HIP(mw::launch_float_env_post(s->d_params, e->ftask, s->dev, s->fdev, e->dev, e->d_asq, o, r, d, to, s->n,
-                                     s->W, 0, s->stream));
-    return MW_OK;
-}
-
-void mw_vecenv_destroy(mw_vecenv* e) {
-    if (!e) return;
-    if (e->sim && e->sim->stream) (void)hipStreamSynchronize(e->sim->stream);
-    if (e->floatenv && e->sim) e->sim->env_owned = false;
-    (void)hipFree(e->d_asq);
-    (void)hipFree(e->d_counters);
-    (void)hipFree(e->d_physics);
-    (void)hipFree(e->d_lane);
-    delete e;
-}
-
-int mw_vecenv_obs_dim(const mw_vecenv* e, int32_t* n) {
-    if (!e || !n) return fail(MW_EINVAL, "null argument");
-    *n = e->task.n_obs;
-    return MW_OK;
-}
-
-int mw_vecenv_reset(mw_vecenv* e, float* obs) {
-    if (!e || !obs) return fail(MW_EINVAL, "null argument");
-    if (e->floatenv) return floatenv_reset(e, obs);
-    mw_sim* s = e->sim;
-    MW_HIP(mw::launch_vecenv_reset(s->d_params, s->n, e->task, s->dev, e->dev, obs, s->W, s->stream));
-    s->host_stale = true;
-    return MW_OK;
-}
-
-static int vec_common(mw_vecenv* e, int32_t T, const void* a, float* o, float* r, uint8_t* d, float* to) {
-    if (!e || !a || !o || !r || !d || !to) return fail(MW_EINVAL, "null argument");
-    if (e->floatenv) {
-        if (T > 0) return fail(MW_EINVAL, "the fused rollout is not available for floating-base envs");
-        return floatenv_step(e, a, o, r, d, to);
-    }
-    if (e->task.n_obs == 4 &&
-        ((reinterpret_cast<uintptr_t>(o) | reinterpret_cast<uintptr_t>(to)) & 15u))
-        return fail(MW_EINVAL, "obs buffers must be 16-byte aligned");
-    mw_sim* s = e->sim;
-    if (e->task.kind == MW_TASK_PANDA_POSITION_TRACKING) {
-        if (T > 0) return fail(MW_EINVAL, "the fused rollout is not available for position-target tasks");
-        // one world per 16-lane row (group_kernel.hip) unless
-        // MWSTEP_PANDA_KERNEL=lane asks for the one-world-per-lane kernel
-        const char* kk = std::getenv("MWSTEP_PANDA_KERNEL");
-        if (kk && std::strcmp(kk, "lane") == 0) {
-            MW_HIP(mw::launch_vecenv_pid_step(s->d_params, s->n, s->topo, needs_cons(s), needs_dual(s), baked_id(s),
-                                              e->task, s->dev, e->dev, pid_set(s), static_cast<const float*>(a), o,
-                                              r, d, to, s->W, static_cast<float>(s->cfg.step_size),
-                                              s->cfg.steps_per_run, s->cfg.pgs_iters, s->stream));
-        } else {
-            // per-dof gains and reset pose: uploaded when they change (a
-            // pageable copy, complete when the call returns; never inside a
-            // captured step, where the gains are fixed)
-            const mw::PidSet ps = pid_set(s);
-            mw::GLaneTask lt[mw::kMaxKernelDofs] = {};
-            for (int k = 0; k < s->n; ++k) {
-                lt[k].pid = ps.g[k];
-                lt[k].home = e->task.home[k];
-            }
-            if (!e->d_lane) MW_HIP(hipMalloc(reinterpret_cast<void**>(&e->d_lane), sizeof(lt)));
-            if (!e->lane_uploaded || std::memcmp(lt, e->h_lane, sizeof(lt)) != 0) {
-                std::memcpy(e->h_lane, lt, sizeof(lt));
-                MW_HIP(hipMemcpyAsync(e->d_lane, e->h_lane, sizeof(lt), hipMemcpyHostToDevice, s->stream));
-                e->lane_uploaded = true;
-            }
-            MW_HIP(mw::launch_vecenv_pid_group(s->d_params, s->n, needs_cons(s), needs_dual(s), e->task, s->dev,
-                                               e->dev, e->d_lane, static_cast<const float*>(a), o, r, d, to, s->W,
-                                               static_cast<float>(s->cfg.step_size), s->cfg.steps_per_run,
-                                               s->cfg.pgs_iters, s->stream));
-        }
-        s->host_stale = true;
-        s->iterations += s->cfg.steps_per_run;
-        s->stepped = true;
-        return MW_OK;
-    }
-    MW_HIP(mw::launch_vecenv_step(s->d_params, s->n, needs_cons(s), needs_dual(s), baked_id(s), e->task, s->dev, e->dev,
-                                  a, o, r, d, to, s->W, static_cast<float>(s->cfg.step_size),
-                                  s->cfg.steps_per_run, s->cfg.pgs_iters, T, s->stream));
-    s->host_stale = true;
-    s->iterations += static_cast<int64_t>(s->cfg.steps_per_run) * (T > 0 ? T : 1);
-    s->stepped = true;
-    return MW_OK;
-}
-
-int mw_vecenv_step(mw_vecenv* e, const void* a, float* o, float* r, uint8_t* d, float* to) {
-    return vec_common(e, 0, a, o, r, d, to);
-}
-
-int mw_vecenv_rollout(mw_vecenv* e, int32_t T, const void* a, float* o, float* r, uint8_t* d, float* to) {
-    if (T <= 0) return fail(MW_EINVAL, "T must be positive");
-    return vec_common(e, T, a, o, r, d, to);
-}
-
-int mw_vecenv_physics(mw_vecenv* e, float* mass, float* gz) {
-    if (!e || !mass || !gz) return fail(MW_EINVAL, "null argument");
-    if (!e->d_physics) return fail(MW_ESTATE, "the env was created without physics randomisation");
-    const size_t nw = static_cast<size_t>(e->sim->n) * e->sim->W;
-    MW_HIP(hipMemcpyAsync(mass, e->dev.rmass, nw * sizeof(float), hipMemcpyDeviceToDevice, e->sim->stream));
-    MW_HIP(hipMemcpyAsync(gz, e->dev.rgz, e->sim->W * sizeof(float), hipMemcpyDeviceToDevice, e->sim->stream));
-    return MW_OK;
-}
-
-int mw_vecenv_counters(mw_vecenv* e, uint32_t* episode, uint32_t* steps) {
-    if (!e || !episode || !steps) return fail(MW_EINVAL, "null argument");
-    const size_t bytes = static_cast<size_t>(e->sim->W) * sizeof(uint32_t);
-    MW_HIP(hipMemcpyAsync(episode, e->dev.episode, bytes, hipMemcpyDeviceToDevice, e->sim->stream));
-    MW_HIP(hipMemcpyAsync(steps, e->dev.steps, bytes, hipMemcpyDeviceToDevice, e->sim->stream));
     return MW_OK;
 }
 

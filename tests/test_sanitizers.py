@@ -1,6 +1,6 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer builds of the host code
 (SURVEY.md §5's sanitizer item; CPU only -- GPU sanitizers are not available
-on the MI355X pool).  tests/sanitize/Makefile builds three drivers with
+on the MI355X pool).  tests/sanitize/Makefile builds four drivers with
 `-fsanitize=address,undefined -fno-sanitize-recover=all`:
 
   * oracle_san  -- the fp64 oracle (oracle/oracle.c): fixed-base steps with
@@ -12,7 +12,11 @@ on the MI355X pool).  tests/sanitize/Makefile builds three drivers with
     OBJ, COLLADA) and malformed inputs that must be rejected;
   * hostdyn_san -- the device dynamics compiled for the host
     (tests/host_dyn/harness.cpp): chain / tree substeps with constraint rows
-    and the floating-tree step with contacts.
+    and the floating-tree step with contacts;
+  * lifecycle_san -- the library's host layer (csrc/sim.cpp, vecenv.cpp,
+    scene.cpp) over a stand-in for the HIP runtime (hip_standin.cpp): every
+    handle's life from create to destroy, cleanly and with each creating call
+    (buffer, stream, event) failing in turn.
 
 Any sanitizer report aborts the driver (non-zero exit, the report on
 stderr).  The sanitized results must also equal the unsanitized oracle's
@@ -37,7 +41,7 @@ ENV = dict(os.environ, ASAN_OPTIONS="abort_on_error=0:halt_on_error=1:detect_lea
 @pytest.fixture(scope="module")
 def san(tmp_path_factory):
     out = str(tmp_path_factory.mktemp("san"))
-    subprocess.run(["make", "-s", "-C", SAN_DIR, f"OUT={out}", "-j3"], check=True)
+    subprocess.run(["make", "-s", "-C", SAN_DIR, f"OUT={out}", "-j4"], check=True)
     return out
 
 
@@ -274,3 +278,31 @@ def test_device_dynamics_on_host_under_sanitizers(san, oracle, panda_file, cartp
         n_contact += len(ow.contacts) > 0
         worst = max(worst, float(np.abs(raw[13 + n:] - ow.qd).max()))
     assert n_contact >= 5 and worst <= 1e-3, (n_contact, worst)
+
+
+# Creating calls (hipMalloc, hipHostMalloc, stream, event) each scenario of
+# tests/sanitize/lifecycle_driver.cpp reaches, measured with the same driver on
+# the sources before the handles owned their resources (where
+# all but the first one or two of each row leaked).  The allocations and their
+# order have not changed since, so fewer points would mean the driver no longer
+# reaches them.
+LIFECYCLE_POINTS = {"sim_cartpole": 10, "sim_cube": 20, "sim_icub": 20, "env_cartpole": 12, "env_panda": 12,
+                    "scene_create": 21, "scene_run": 21, "scene_big": 24}
+
+
+def test_handles_own_their_resources_under_sanitizers(san):
+    """Simulator, CartPole env, Panda env and scenes at 8 worlds, once cleanly
+    and once per creating call with that call failing (MW_EHIP and a message),
+    every later call up to the destroy included: no sanitizer report, and after
+    every destroy as many live buffers, streams and events as before."""
+    lines = _run(san, "lifecycle_san", MODELS).strip().split("\n")
+    got = {}
+    for line in lines:
+        name, _, points, _, leaks = line.split()
+        got[name] = (int(points), int(leaks))
+    assert set(got) == set(LIFECYCLE_POINTS), lines
+    for name, before in LIFECYCLE_POINTS.items():
+        points, leaks = got[name]
+        assert leaks == 0, lines
+        # every injection loop ended at a clean run (the driver's cap is 1000)
+        assert before <= points < 1000, (name, points, before)
