@@ -7,6 +7,12 @@
 //   float_env_post_kernel     obs / reward / done, and for the done worlds the
 //                             pending resets the next run's first launch applies
 //
+// With randomisation on (mw_floatenv_randomize) the launches stay these three:
+// the post launch's PUSH instance reports the push the run applied and writes
+// the next step's into the run kernel's wrench array, its RAND instance draws
+// the friction of every episode it starts into the simulator's per-world
+// array (T.rand.mu).
+//
 // Both kernels are transposes between the row-major [W, k] tensors of the
 // agent and the [k][W] SoA arrays of the simulator.  A block of 256 threads
 // owns a tile of 64 worlds and stages it through LDS, so the row side moves
@@ -75,6 +81,19 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_action_kernel(const flo
 // mw_reset_base_pose + mw_reset_base_velocity leave on the device), the
 // divergence flag re-armed, and the reset state's observation.  reset_all:
 // every world starts episode 0 (mw_vecenv_reset), only obs is written.
+// RAND (friction randomisation, T.rand.friction_hi > 0): a reset also draws
+// the friction coefficient of the episode it starts, U(friction_lo,
+// friction_hi) from the episode block, into T.rand.mu -- the next run reads
+// it together with the pending reset -- and T.rand.friction_out.
+// PUSH (T.rand.push_interval > 0): node 0 of the run kernel's wrench array
+// [6][wnodes][W] holds the world wrench on the base that the run before this
+// launch applied; it goes to T.rand.push_out [W, 6], and the wrench of the
+// world's next step takes its place -- zeros where no push is active; the
+// other nodes stay zero from allocation.  The schedule is a pure function of
+// (seed, global world, episode, steps taken), all known here once the counters
+// are updated: the episode's phase from its episode block, push k's (fx, fy,
+// tz) from block kFtPushBlock | k (float_task.hpp).
+template <bool RAND, bool PUSH>
 __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const ChainF* __restrict__ P, FloatTaskF T,
                                                                      SimDev S, FreeDev D, VecDev V,
                                                                      const float* __restrict__ asq,
@@ -86,6 +105,7 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
     extern __shared__ float tile[];  // [kEnvTile][n_obs | 1]: the observation rows
     __shared__ uint8_t s_done[kEnvTile];
     __shared__ uint32_t s_episode[kEnvTile];
+    __shared__ uint32_t s_steps[kEnvTile];  // PUSH: steps taken in the episode the next step belongs to
     const int NO = T.n_obs, pitch = NO | 1;
     const int w0 = blockIdx.x * kEnvTile;
     const int rows = min(kEnvTile, W - w0);
@@ -137,6 +157,7 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
             }
             s_done[lane] = done ? 1 : 0;
             s_episode[lane] = episode;
+            if (PUSH) s_steps[lane] = live ? V.steps[w] : 0u;
         }
         __syncthreads();
         // the finished episodes' last observation: row r of the tile, lanes across its words
@@ -148,12 +169,33 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
         if (wave == 0) {
             s_done[lane] = live ? 1 : 0;
             s_episode[lane] = 0u;
+            if (PUSH) s_steps[lane] = 0u;
             if (live) {
                 V.episode[w] = 0u;
                 V.steps[w] = 0u;
             }
         }
         __syncthreads();
+    }
+    if (PUSH && wave == 2 && live) {
+        const size_t node = static_cast<size_t>(D.wnodes) * Ws;  // words per wrench component
+        if (!reset_all && T.rand.push_out) {
+#pragma unroll
+            for (int e = 0; e < 6; ++e) T.rand.push_out[static_cast<size_t>(w) * 6 + e] = D.wrench[e * node + w];
+        }
+        const uint32_t g = T.world_offset + static_cast<uint32_t>(w), episode = s_episode[lane];
+        uint32_t r[4], k;
+        philox(T.seed_lo, T.seed_hi, g, episode, r, kFtEpisodeBlock);
+        float f[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (ft_push_active(s_steps[lane], ft_push_phase(r[0], T.rand.push_interval), T.rand.push_interval,
+                           T.rand.push_steps, k)) {
+            philox(T.seed_lo, T.seed_hi, g, episode, r, ft_push_block(k));
+            f[0] = unif(r[0], -T.rand.push_force, T.rand.push_force);
+            f[1] = unif(r[1], -T.rand.push_force, T.rand.push_force);
+            f[5] = unif(r[2], -T.rand.push_torque, T.rand.push_torque);
+        }
+#pragma unroll
+        for (int e = 0; e < 6; ++e) D.wrench[e * node + w] = f[e];
     }
     // resets: home pose + U(-noise, noise) per joint clipped into the position
     // limits, Philox counter (global world, episode, block of 4 dofs, 0) as
@@ -192,6 +234,13 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
             D.rflag[w] = 1u | 2u;
             S.div[w] = 0;  // a reset re-arms the divergence flag (mw_reset_* do)
         }
+        if (RAND && wave == 1) {
+            uint32_t r[4];
+            philox(T.seed_lo, T.seed_hi, T.world_offset + static_cast<uint32_t>(w), episode, r, kFtEpisodeBlock);
+            const float mu = unif(r[1], T.rand.friction_lo, T.rand.friction_hi);
+            T.rand.mu[w] = mu;
+            if (T.rand.friction_out) T.rand.friction_out[w] = mu;
+        }
         for (int j = wave; j < T.n_links; j += kEnvWaves) row[13 + 2 * n + j] = 0.f;
     }
     __syncthreads();
@@ -213,9 +262,16 @@ hipError_t launch_float_env_post(const ChainF* P, const FloatTaskF& T, const Sim
                                  const VecDev& V, const float* asq, float* obs, float* reward, uint8_t* done,
                                  float* term_obs, int n, int W, int reset_all, hipStream_t st) {
     const size_t lds = static_cast<size_t>(dev::kEnvTile) * (T.n_obs | 1) * sizeof(float);
-    hipLaunchKernelGGL(dev::float_env_post_kernel, dim3((W + dev::kEnvTile - 1) / dev::kEnvTile),
-                       dim3(dev::kEnvThreads), lds, st, P, T, S, D, V, asq, obs, reward, done, term_obs, n, W,
-                       reset_all);
+    const dim3 grid((W + dev::kEnvTile - 1) / dev::kEnvTile), block(dev::kEnvThreads);
+    const bool rand = T.rand.friction_hi > 0.f, push = T.rand.push_interval > 0u;
+#define MW_POST(R_, P_)                                                                                          \
+    hipLaunchKernelGGL((dev::float_env_post_kernel<R_, P_>), grid, block, lds, st, P, T, S, D, V, asq, obs, reward, \
+                       done, term_obs, n, W, reset_all)
+    if (rand && push) MW_POST(true, true);
+    else if (rand) MW_POST(true, false);
+    else if (push) MW_POST(false, true);
+    else MW_POST(false, false);
+#undef MW_POST
     return hipGetLastError();
 }
 

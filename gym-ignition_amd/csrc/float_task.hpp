@@ -3,7 +3,9 @@
 // the stored body twist, tilt, reward and the termination predicate, float32.
 // Plain inline functions: the post kernel calls them per world, and
 // tests/host_float_task/harness.cpp builds the same code with g++ against
-// numpy fp64.  The Philox reset sampling stays in rng.hpp (device only).
+// numpy fp64.  The Philox reset sampling stays in rng.hpp (device only); the
+// integer arithmetic of the push schedule (mw_floatenv_randomize) is here too,
+// built by tests/host_float_rand/harness.cpp.
 #pragma once
 
 #ifdef MW_HOST_TEST
@@ -27,6 +29,24 @@ namespace mw {
 
 constexpr int kMaxContactLinks = 8;  // mw_float_task_config::contact_links
 
+// Randomisation of the floating-base env (mw_floatenv_randomize): pushes on
+// the base and per-world ground friction, all off when zero.
+struct FloatRandF {
+    uint32_t push_interval;  // steps between push starts, 0 = no pushes
+    uint32_t push_steps;     // steps a push lasts, 1..push_interval
+    float push_force;        // fx, fy ~ U(-push_force, push_force) (N)
+    float push_torque;       // tz ~ U(-push_torque, push_torque) (N m)
+    float friction_lo, friction_hi;  // mu ~ U(lo, hi) per episode; on when hi > 0
+    float* push_out;         // [W, 6] the wrench applied this step (caller's, may be null)
+    float* friction_out;     // [W] the friction coefficient of the current episode (caller's, may be null)
+    float* mu;               // [W] the simulator's per-world friction array (mw_sim::d_mu) when friction_hi > 0
+};
+
+// Philox counter blocks of the randomisation draws: the reset draw uses
+// blocks 0 .. (n + 3) / 4 - 1 of the same (world, episode) counter.
+constexpr uint32_t kFtEpisodeBlock = 0x40000000u;  // r[0]: push phase, r[1]: friction
+constexpr uint32_t kFtPushBlock = 0x80000000u;     // | k: push k of the episode (fx, fy, tz)
+
 // Task description of the floating-base env (kernel argument, by value).
 struct FloatTaskF {
     int32_t action_mode;     // 0 torque (SimDev::cmd), 1 position (SimDev::ptgt)
@@ -41,9 +61,25 @@ struct FloatTaskF {
     float home_base[7];      // x y z qw qx qy qz
     uint32_t link_slots[kMaxContactLinks];  // contact slots (FreeDev::cmask bits) of every contact link
     float home_q[kMaxBodies];
+    FloatRandF rand;
 };
 
 namespace dev {
+
+// The push schedule is a pure function of (seed, global world, episode, t), t
+// the steps already taken in the episode: the episode's phase shifts a grid
+// of period push_interval, push k = (t + phase) / interval is active while
+// (t + phase) % interval < push_steps.
+__device__ __forceinline__ uint32_t ft_push_phase(uint32_t r0, uint32_t interval) {
+    return interval ? r0 % interval : 0u;
+}
+__device__ __forceinline__ bool ft_push_active(uint32_t t, uint32_t phase, uint32_t interval, uint32_t push_steps,
+                                               uint32_t& k) {
+    const uint32_t s = t + phase;
+    k = s / interval;
+    return s % interval < push_steps;
+}
+__device__ __forceinline__ uint32_t ft_push_block(uint32_t k) { return kFtPushBlock | k; }
 
 // The rotation of the base (row-major, body -> world) from its unit
 // quaternion: the matrix mw_get_base_velocity rotates the body twist with.

@@ -403,7 +403,7 @@ __device__ __forceinline__ float dof_force(const ChainF* __restrict__ P, const S
     return tau;
 }
 
-template <int MAXN, bool CONS>
+template <int MAXN, bool CONS, bool WMU>
 __global__ void __launch_bounds__(64, 1) wave_run_kernel(const ChainF* __restrict__ P, const FloatF* __restrict__ F,
                                                       int N, SimDev S, FreeDev D, const PidF* __restrict__ pid,
                                                       int W, RunArgs A, int want_contacts, int* __restrict__ overflow) {
@@ -488,6 +488,9 @@ __global__ void __launch_bounds__(64, 1) wave_run_kernel(const ChainF* __restric
 #endif
     // the first substep's joint forces from the preloaded PID inputs (pre0
     // dies here instead of living through the substep loop)
+    // WMU: per-world ground friction (mw_set_ground_friction), else the model's;
+    // w is wave-uniform, so either way the step reads it with one scalar load
+    const float* __restrict__ mu_w = WMU ? A.mu + w : &F->mu;
     float tau0 = 0.f;
     if (!A.paused && lane < N) tau0 = dof_force(P, S, pid, W, w, A, 0, lane, act, cmd, vc, q, qd, &pre0);
     if (!A.paused) {
@@ -498,7 +501,7 @@ __global__ void __launch_bounds__(64, 1) wave_run_kernel(const ChainF* __restric
             MW_PROF_T(tb);
             MW_PROF_ACC(0, ta, tb);
             active = wave_step<MAXN, CONS>(P, F, N, base, L, A.dt, A.pgs_iters, A.pgs_tol, A.warm != 0,
-                                           A.lcp_solves, L.qdd, &ovf, &unconv, prof, A.wrenches != 0);
+                                           A.lcp_solves, L.qdd, &ovf, &unconv, prof, A.wrenches != 0, mu_w);
             MW_PROF_T(tc);
             MW_PROF_ACC(7, ta, tc);
         }
@@ -759,35 +762,43 @@ extern "C" int mw_debug_wave_prof(unsigned long long* out) {
 }
 #endif
 
+template <int MAXN>
+static void wave_launch(bool cons, dim3 grid, dim3 block, hipStream_t st, const ChainF* P, const FloatF* F,
+                        int n, const SimDev& S, const FreeDev& D, const PidF* pid, int W, const RunArgs& a,
+                        int contacts, int* overflow) {
+    const bool wmu = a.mu != nullptr;
+    if (cons && wmu)
+        hipLaunchKernelGGL((dev::wave_run_kernel<MAXN, true, true>), grid, block, 0, st, P, F, n, S, D, pid, W, a,
+                           contacts, overflow);
+    else if (cons)
+        hipLaunchKernelGGL((dev::wave_run_kernel<MAXN, true, false>), grid, block, 0, st, P, F, n, S, D, pid, W, a,
+                           contacts, overflow);
+    else if (wmu)
+        hipLaunchKernelGGL((dev::wave_run_kernel<MAXN, false, true>), grid, block, 0, st, P, F, n, S, D, pid, W, a,
+                           contacts, overflow);
+    else
+        hipLaunchKernelGGL((dev::wave_run_kernel<MAXN, false, false>), grid, block, 0, st, P, F, n, S, D, pid, W, a,
+                           contacts, overflow);
+}
+
 hipError_t launch_wave_run(const ChainF* P, int n, int depth, bool cons, const FloatF* F, const SimDev& S,
                            const FreeDev& D, const PidF* pid, int W, const RunArgs& a, int contacts, int* overflow,
                            hipStream_t st) {
     const dim3 grid(static_cast<unsigned>(W)), block(dev::kWaveLanes);
     if (depth > dev::kWaveMaxDepth) return hipErrorInvalidValue;
-    if (n <= 16 && depth <= dev::WaveWorld<16>::kDepth) {
-        if (cons)
-            hipLaunchKernelGGL((dev::wave_run_kernel<16, true>), grid, block, 0, st, P, F, n, S, D, pid, W, a,
-                               contacts, overflow);
-        else
-            hipLaunchKernelGGL((dev::wave_run_kernel<16, false>), grid, block, 0, st, P, F, n, S, D, pid, W, a,
-                               contacts, overflow);
-    } else if (n <= 32) {
-        if (cons)
-            hipLaunchKernelGGL((dev::wave_run_kernel<32, true>), grid, block, 0, st, P, F, n, S, D, pid, W, a,
-                               contacts, overflow);
-        else
-            hipLaunchKernelGGL((dev::wave_run_kernel<32, false>), grid, block, 0, st, P, F, n, S, D, pid, W, a,
-                               contacts, overflow);
-    } else if (n <= kMaxBodies) {
-        if (cons)
-            hipLaunchKernelGGL((dev::wave_run_kernel<kMaxBodies, true>), grid, block, 0, st, P, F, n, S, D, pid, W,
-                               a, contacts, overflow);
-        else
-            hipLaunchKernelGGL((dev::wave_run_kernel<kMaxBodies, false>), grid, block, 0, st, P, F, n, S, D, pid, W,
-                               a, contacts, overflow);
-    } else {
+    // the per-world friction read is its own instantiation (WMU), picked here
+    // when the simulator has the array: in the shared one the extra live
+    // pointer moved the register allocation and cost the quadruped leg 1 %
+    // (DESIGN 3.6b), so a simulator without the array (RunArgs::mu null) runs the
+    // kernel as it was
+    if (n <= 16 && depth <= dev::WaveWorld<16>::kDepth)
+        wave_launch<16>(cons, grid, block, st, P, F, n, S, D, pid, W, a, contacts, overflow);
+    else if (n <= 32)
+        wave_launch<32>(cons, grid, block, st, P, F, n, S, D, pid, W, a, contacts, overflow);
+    else if (n <= kMaxBodies)
+        wave_launch<kMaxBodies>(cons, grid, block, st, P, F, n, S, D, pid, W, a, contacts, overflow);
+    else
         return hipErrorInvalidValue;
-    }
     return hipGetLastError();
 }
 

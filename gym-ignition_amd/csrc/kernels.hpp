@@ -69,6 +69,9 @@ struct RunArgs {
     int warm;             // PGS starts from the previous step's impulses (wave kernel)
     int lcp_solves;       // > 0: the wave kernel solves its boxed LCP exactly within that many linear solves
     int wrenches;         // FreeDev::wrench holds this launch's world wrenches
+    // [W] per-world ground friction in device memory (wave kernel,
+    // mw_set_ground_friction), or null: every world takes FloatF::mu
+    const float* mu;
 };
 
 // Task description for the device-side env (see sim.cpp for the sources).
@@ -169,6 +172,12 @@ hipError_t launch_vecenv_pid_group(const ChainF* P, int n, bool cons, bool dual,
 // reset_all: every world starts episode 0, only obs is written.
 hipError_t launch_float_env_action(const float* actions, float* out, float* asq, uint8_t* div,
                                    unsigned long long* ndiv, int n, int W, hipStream_t st);
+// With randomisation on (mw_floatenv_randomize, T.rand) the post launch also
+// copies the base wrench the run applied (node 0 of D.wrench) into
+// T.rand.push_out and writes the next step's in its place (zeros where no push
+// is active), where T.rand.push_interval > 0; and writes the friction of every
+// episode it starts into T.rand.mu and T.rand.friction_out, where
+// T.rand.friction_hi > 0.
 hipError_t launch_float_env_post(const ChainF* P, const struct FloatTaskF& T, const SimDev& S, const FreeDev& D,
                                  const VecDev& V, const float* asq, float* obs, float* reward, uint8_t* done,
                                  float* term_obs, int n, int W, int reset_all, hipStream_t st);

@@ -74,7 +74,62 @@ mw::PidSet pid_set(const mw_sim* s) {
     return P;
 }
 
+// The wrench array of the wave kernel for an env that fills it on the device:
+// all zeros (the env writes node 0 only).  A buffer mw_apply_link_wrench
+// allocated is kept: its staging copy rewrites it whole.
+int alloc_env_wrench(mw_sim* s) {
+    const int nn = s->n + 1;
+    const size_t bytes = 6 * static_cast<size_t>(nn) * s->W * sizeof(float);
+    if (!s->d_ext) MW_HIP(mw::dev_alloc(s->d_ext, bytes));
+    MW_HIP(hipMemsetAsync(s->d_ext.get(), 0, bytes, s->stream));
+    s->fdev.wrench = s->d_ext.get();
+    s->fdev.wnodes = nn;
+    return MW_OK;
+}
+
+// The per-world friction array, every world at the current coefficient (the
+// float32 FloatF::mu holds): allocate, fill, then publish.
+int alloc_ground_friction(mw_sim* s) {
+    if (s->d_mu) return MW_OK;
+    const size_t W = static_cast<size_t>(s->W);
+    mw::dev_ptr<float[]> d;
+    MW_HIP(mw::dev_alloc(d, W * sizeof(float)));
+    s->h_mu.assign(W, static_cast<float>(s->ground_mu));
+    MW_HIP(hipMemcpyAsync(d.get(), s->h_mu.data(), W * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    MW_HIP(hipStreamSynchronize(s->stream));  // h_mu is pageable and rewritten by the setters
+    s->d_mu = std::move(d);
+    return MW_OK;
+}
+
+// device -> host mirror of the friction array (an env's kernels wrote it)
+int pull_ground_friction(mw_sim* s) {
+    if (!s->d_mu) return MW_OK;
+    MW_HIP(hipMemcpyAsync(s->h_mu.data(), s->d_mu.get(), static_cast<size_t>(s->W) * sizeof(float),
+                          hipMemcpyDeviceToHost, s->stream));
+    MW_HIP(hipStreamSynchronize(s->stream));
+    return MW_OK;
+}
+
 namespace {
+
+// host mirror -> device, worlds [w0, w0 + nw)
+int upload_ground_friction(mw_sim* s, int32_t w0, int32_t nw) {
+    if (nw <= 0) return MW_OK;
+    MW_HIP(hipSetDevice(s->cfg.device));
+    MW_HIP(hipMemcpyAsync(s->d_mu.get() + w0, s->h_mu.data() + w0, static_cast<size_t>(nw) * sizeof(float),
+                          hipMemcpyHostToDevice, s->stream));
+    MW_HIP(hipStreamSynchronize(s->stream));  // the pageable mirror may be rewritten at once
+    return MW_OK;
+}
+
+// ... and of the per-world ground friction while an env randomises it
+int check_not_env_friction(const mw_sim* s, const char* what) {
+    if (s && s->env_friction)
+        return fail(MW_ESTATE, std::string(what) + ": a floating-base env with friction randomisation owns this "
+                                                   "simulator's per-world ground friction (it lives on the "
+                                                   "device); destroy the env first");
+    return MW_OK;
+}
 
 // Host setters of commands / pending resets on a simulator that a
 // floating-base env drives: the env writes the same device arrays from its
@@ -939,12 +994,15 @@ int run_impl(mw_sim* s, int paused, bool readback) {
     a.warm = (s->wave && (s->pgs_warm || a.lcp_solves > 0) && s->d_warm) ? 1 : 0;
     if (a.lcp_solves > 0) a.pgs_tol = std::max(a.pgs_tol, kExactPgsTol);
     a.first = 1;
+    a.mu = s->wave ? s->d_mu.get() : nullptr;
     const int spr = s->cfg.steps_per_run;
     int done = 0;
     do {
         int chunk = paused ? 0 : std::min(64, spr - done);
         a.wrenches = 0;
-        if (chunk > 0 && s->d_ext && s->wr_until > s->iterations + done) {
+        if (chunk > 0 && s->env_wrench) {
+            a.wrenches = 1;  // the env's post launch wrote d_ext on the device: nothing to stage
+        } else if (chunk > 0 && s->d_ext && s->wr_until > s->iterations + done) {
             if (int rc2 = stage_wrenches(s, s->iterations + done, chunk)) return rc2;
             a.wrenches = 1;
         }
@@ -1581,6 +1639,9 @@ int mw_apply_link_wrench(mw_sim* s, int32_t link, int32_t w0, int32_t nw, const 
         return fail(MW_ESTATE, "world wrenches on mw_sim need the world-per-wavefront kernel (articulated floating "
                                "bases, generic fixed-base trees); fixed-base chains and free bodies take them "
                                "through a scene (mw_scene_apply_world_wrench)");
+    if (s->env_wrench)
+        return fail(MW_ESTATE, "mw_apply_link_wrench: a floating-base env with pushes owns this simulator's wrench "
+                               "buffer (its kernels write it on the device); destroy the env first");
     if (link < -1 || link >= s->n) return fail(MW_EINVAL, "link index out of range");
     if (!(duration >= 0.0)) return fail(MW_EINVAL, "the wrench duration must be >= 0");
     const int nn = s->n + 1;
@@ -1656,11 +1717,50 @@ int mw_pgs_options(const mw_sim* s, double* tol, int32_t* warm_start) {
 int mw_set_ground_plane(mw_sim* s, int32_t enabled, double mu) {
     if (!s) return fail(MW_EINVAL, "null simulator handle");
     if (!(mu >= 0.0)) return fail(MW_EINVAL, "the friction coefficient must be >= 0");
+    if (int own = check_not_env_friction(s, "mw_set_ground_plane")) return own;
     s->ground = enabled != 0;
     s->ground_mu = mu;
+    if (s->d_mu) {  // every world takes mu
+        std::fill(s->h_mu.begin(), s->h_mu.end(), static_cast<float>(mu));
+        if (int rc = upload_ground_friction(s, 0, s->W)) return rc;
+    }
     if (s->fbase() && s->initialized) return upload_params(s);
     if (s->float_tree && s->loaded) build_float(s);
     else if (s->floating && s->loaded) build_free(s);
+    return MW_OK;
+}
+
+// Per-world friction coefficients of the ground plane (wave kernel): the
+// float32 values the run kernel reads from mw_sim::d_mu, from the next run on.
+int mw_set_ground_friction(mw_sim* s, int32_t w0, int32_t nw, const double* mu) {
+    if (!s || !s->loaded) return fail(MW_ESTATE, "no model loaded");
+    if (!s->initialized) return fail(MW_ESTATE, "the simulator is not initialized");
+    if (!mu && nw > 0) return fail(MW_EINVAL, "null argument");
+    if (w0 < 0 || nw < 0 || w0 + nw > s->W) return fail(MW_EINVAL, "world range out of bounds");
+    if (!s->wave)
+        return fail(MW_ESTATE, "per-world ground friction on mw_sim needs the world-per-wavefront kernel (articulated "
+                               "floating bases, generic fixed-base trees); other models take one coefficient for "
+                               "all worlds (mw_set_ground_plane) or per-world friction through a scene "
+                               "(mw_scene_set_world_friction)");
+    if (int own = check_not_env_friction(s, "mw_set_ground_friction")) return own;
+    for (int32_t k = 0; k < nw; ++k)
+        if (!(mu[k] >= 0.0)) return fail(MW_EINVAL, "the friction coefficient must be >= 0");
+    MW_HIP(hipSetDevice(s->cfg.device));
+    if (int rc = alloc_ground_friction(s)) return rc;
+    for (int32_t k = 0; k < nw; ++k) s->h_mu[w0 + k] = static_cast<float>(mu[k]);
+    return upload_ground_friction(s, w0, nw);
+}
+
+int mw_ground_friction(mw_sim* s, int32_t w0, int32_t nw, double* mu) {
+    if (!s || !s->loaded) return fail(MW_ESTATE, "no model loaded");
+    if (!s->initialized) return fail(MW_ESTATE, "the simulator is not initialized");
+    if (!mu && nw > 0) return fail(MW_EINVAL, "null argument");
+    if (w0 < 0 || nw < 0 || w0 + nw > s->W) return fail(MW_EINVAL, "world range out of bounds");
+    if (s->env_friction) {  // the env's kernels write the array
+        MW_HIP(hipSetDevice(s->cfg.device));
+        if (int rc = pull_ground_friction(s)) return rc;
+    }
+    for (int32_t k = 0; k < nw; ++k) mu[k] = s->d_mu ? s->h_mu[w0 + k] : static_cast<float>(s->ground_mu);
     return MW_OK;
 }
 

@@ -118,6 +118,17 @@ struct mw_sim {
     mw::dev_ptr<float[]> d_ext;    // [6][node][W]: the summed wrenches of one launch
     mw::pin_ptr<float[]> h_ext;    // pinned staging of d_ext
     int64_t wr_until = 0;
+    // an env with pushes (mw_floatenv_randomize) writes d_ext on the device:
+    // every run passes it to the kernel as it is (no staging, no
+    // synchronisation), and mw_apply_link_wrench fails with MW_ESTATE
+    bool env_wrench = false;
+    // per-world ground friction (mw_set_ground_friction, wave kernel): [W] on
+    // the device (RunArgs::mu) and its host mirror; allocated by the first call
+    mw::dev_ptr<float[]> d_mu;
+    std::vector<float> h_mu;
+    // an env with friction randomisation writes d_mu on the device: the host
+    // setters fail with MW_ESTATE, mw_ground_friction reads the device copy
+    bool env_friction = false;
     mw::pin_ptr<int[]> h_overflow;  // pinned copy read back with each synchronous run
     int64_t overflow_seen = 0;    // drops already reported
     // divergence detection: [W] sticky per-world flags + the uint64 count of
@@ -160,3 +171,8 @@ bool needs_cons(const mw_sim* s);
 bool needs_dual(const mw_sim* s);
 int baked_id(const mw_sim* s);
 mw::PidSet pid_set(const mw_sim* s);
+// allocate the device arrays an env's randomisation writes (zeroed wrenches
+// [6][n + 1][W]; friction [W] filled with the current coefficient)
+int alloc_env_wrench(mw_sim* s);
+int alloc_ground_friction(mw_sim* s);
+int pull_ground_friction(mw_sim* s);  // device copy -> host mirror (synchronises)

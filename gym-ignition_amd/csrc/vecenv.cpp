@@ -30,6 +30,7 @@ struct mw_vecenv {
     bool floatenv = false;
     mw::FloatTaskF ftask{};
     mw::dev_ptr<float[]> d_asq;
+    bool was_reset = false;  // mw_vecenv_reset ran: mw_floatenv_randomize comes too late
 
     // the env's work (on its simulator's stream) drains before the members release their buffers
     ~mw_vecenv() { if (sim && sim->stream) (void)hipStreamSynchronize(sim->stream); }
@@ -227,8 +228,52 @@ int mw_floatenv_create(mw_sim* s, const mw_float_task_config* cfg, mw_vecenv** o
     return MW_OK;
 }
 
+// Pushes and friction randomisation of a floating-base env: the post launch
+// (and the reset's) fills the wave kernel's wrench array with the next step's
+// push, which run_impl then passes on as it is, and draws the friction of
+// every episode it resets into the simulator's per-world array.
+int mw_floatenv_randomize(mw_vecenv* e, const mw_float_rand_config* cfg, float* push_out, float* friction_out) {
+    if (!e || !cfg) return fail(MW_EINVAL, "null argument");
+    if (!e->floatenv) return fail(MW_ESTATE, "mw_floatenv_randomize needs an env made by mw_floatenv_create");
+    if (e->was_reset) return fail(MW_ESTATE, "mw_floatenv_randomize must be called before the first mw_vecenv_reset");
+    if (cfg->push_interval < 0) return fail(MW_EINVAL, "push_interval must be >= 0");
+    if (cfg->push_interval > 0 && (cfg->push_steps < 1 || cfg->push_steps > cfg->push_interval))
+        return fail(MW_EINVAL, "push_steps must be in [1, push_interval]");
+    if (!(cfg->push_force >= 0.f) || !(cfg->push_torque >= 0.f))
+        return fail(MW_EINVAL, "push_force and push_torque must be >= 0");
+    if (!(cfg->friction_lo >= 0.f) || !(cfg->friction_hi >= cfg->friction_lo))
+        return fail(MW_EINVAL, "the friction range needs 0 <= friction_lo <= friction_hi");
+    mw_sim* s = e->sim;
+    const bool push = cfg->push_interval > 0, friction = cfg->friction_hi > 0.f;
+    MW_HIP(hipSetDevice(s->cfg.device));
+    // the allocations first: a failed call leaves the env as it was
+    if (push && !s->env_wrench)
+        if (int rc = alloc_env_wrench(s)) return rc;
+    if (friction)
+        if (int rc = alloc_ground_friction(s)) return rc;
+    mw::FloatRandF& R = e->ftask.rand;
+    R = mw::FloatRandF{};
+    if (push) {
+        R.push_interval = static_cast<uint32_t>(cfg->push_interval);
+        R.push_steps = static_cast<uint32_t>(cfg->push_steps);
+        R.push_force = cfg->push_force;
+        R.push_torque = cfg->push_torque;
+        R.push_out = push_out;
+    }
+    if (friction) {
+        R.friction_lo = cfg->friction_lo;
+        R.friction_hi = cfg->friction_hi;
+        R.friction_out = friction_out;
+        R.mu = s->d_mu.get();
+    }
+    s->env_wrench = push;
+    s->env_friction = friction;
+    return MW_OK;
+}
+
 static int floatenv_reset(mw_vecenv* e, float* obs) {
     mw_sim* s = e->sim;
+    e->was_reset = true;
     MW_HIP(mw::launch_float_env_post(s->d_params.get(), e->ftask, s->dev, s->fdev, e->dev, e->d_asq.get(), obs,
                                      nullptr, nullptr, nullptr, s->n, s->W, 1, s->stream));
     // a paused run applies the pending resets: the state (and the host
@@ -250,7 +295,17 @@ static int floatenv_step(mw_vecenv* e, const void* a, float* o, float* r, uint8_
 
 void mw_vecenv_destroy(mw_vecenv* e) {
     if (!e) return;
-    if (e->floatenv && e->sim) e->sim->env_owned = false;
+    if (e->floatenv && e->sim) {
+        mw_sim* s = e->sim;
+        s->env_owned = false;
+        s->env_wrench = false;
+        if (s->env_friction) {
+            // the simulator keeps the last episode's coefficients: its host mirror takes them over
+            (void)hipSetDevice(s->cfg.device);
+            (void)pull_ground_friction(s);
+            s->env_friction = false;
+        }
+    }
     delete e;
 }
 

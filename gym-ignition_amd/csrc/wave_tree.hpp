@@ -530,12 +530,14 @@ __device__ __forceinline__ void wave_pgs(const WaveWorld<MAXN>& L, const float (
 }
 
 // One engine step of world L (state in L.q / L.qd / base; joint forces in
-// L.tau).  Returns the active slot mask; *overflow += rows dropped.
+// L.tau).  Returns the active slot mask; *overflow += rows dropped.  mu_w:
+// the world's ground friction coefficient (wave-uniform address).
 template <int MAXN, bool CONS>
 __device__ __forceinline__ uint32_t wave_step(const ChainF* __restrict__ P, const FloatF* __restrict__ F, int N,
                                               FreeState& base, WaveWorld<MAXN>& L, float dt, int pgs_iters,
                                               float pgs_tol, bool warm, int lcp_solves, float* qdd_out, int* overflow,
-                                              int* unconverged, unsigned long long* prof, bool ext) {
+                                              int* unconverged, unsigned long long* prof, bool ext,
+                                              const float* __restrict__ mu_w) {
     const int lane = lane_id();
     const int NV = 6 + N;
     MW_PROF_T(t0);
@@ -849,7 +851,7 @@ __device__ __forceinline__ uint32_t wave_step(const ChainF* __restrict__ P, cons
             }
             L.rc[lane] = c;
         }
-        const float mu = F->mu;
+        const float mu = *mu_w;  // this world's ground friction: mw_sim::d_mu[w], or FloatF::mu
         float x[kWaveMaxRows];
         // warm start: every row from the previous step's impulse of the same
         // row identity (contact slot / joint row), else 0; x1w: its stage-1

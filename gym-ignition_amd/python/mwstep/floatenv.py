@@ -19,6 +19,10 @@ While the env exists it owns the simulator's joint commands and pending
 resets: the host setters of ``env.sim`` that write them (``set("force_target"
 | "position_target" | "reset_q" | ...)``, ``reset_base_pose``,
 ``set_control_mode``, ``set_pid``, ``set_state``) raise; the getters work.
+With pushes on it also owns the simulator's wrench buffer
+(``apply_world_wrench`` raises), with friction randomisation on the per-world
+ground friction (``set_ground_friction`` / ``set_ground_plane`` raise,
+``ground_friction()`` reads the device copy).
 """
 
 from __future__ import annotations
@@ -67,7 +71,9 @@ class FloatVecEnv:
                  alive_bonus: float = 1.0, w_forward: float = 1.0, w_action: float = 0.0,
                  w_pose: float = 0.0, joint_noise: float = 0.0, max_episode_steps: int = 1000,
                  seed: int = 42, world_offset: int = 0, step_size: float = 1e-3, steps_per_run: int = 1,
-                 device: int = 0, pgs_iters: int = 20, ground_mu: float = 1.0):
+                 device: int = 0, pgs_iters: int = 20, ground_mu: float = 1.0,
+                 push_interval: int = 0, push_steps: int = 1, push_force: float = 0.0, push_torque: float = 0.0,
+                 friction_range: Optional[Sequence[float]] = None):
         """``model``: a shipped model's name or a URDF / SDF file.  ``home_q``
         (one value per dof) and ``home_base`` (x y z qw qx qy qz) are the reset
         state; ``pid_gains`` per dof ``(p, i, d)`` or the eight values of
@@ -75,7 +81,17 @@ class FloatVecEnv:
         joint names in dof order.  ``contact_links``: link names
         or dof indices (-1 = the base) whose ground reaction enters the
         observation.  ``max_tilt`` (rad): the episode ends when the base's z
-        axis leans further from the world's."""
+        axis leans further from the world's.
+
+        Domain randomisation, sampled on the device (``mw_floatenv_randomize``):
+        ``push_interval`` > 0 pushes every world's base for ``push_steps``
+        steps out of every ``push_interval``, each episode at its own phase,
+        with a world force (fx, fy) ~ U(-``push_force``, ``push_force``) N and a
+        torque tz ~ U(-``push_torque``, ``push_torque``) N m; ``friction_range``
+        ``(lo, hi)`` draws every world's ground friction anew at each reset.
+        ``env.push`` ``[n_worlds, 6]`` holds the wrench the last step applied and
+        ``env.friction`` ``[n_worlds]`` the current coefficients; both are also
+        in ``info`` (``"push"``, ``"friction"``) when the feature is on."""
         torch = _torch()
         if action_mode not in ACTION_MODES:
             raise ValueError(f"unknown action_mode {action_mode!r}; known: {sorted(ACTION_MODES)}")
@@ -135,6 +151,18 @@ class FloatVecEnv:
         self.reward = torch.zeros((n_worlds,), **f32)
         self.done = torch.zeros((n_worlds,), dtype=torch.uint8, device=self.device)
         self.terminal_obs = torch.zeros((n_worlds, self.obs_dim), **f32)
+        self.push = self.friction = None
+        self._info = {"terminal_obs": self.terminal_obs}
+        if push_interval or friction_range is not None:
+            lo, hi = (0.0, 0.0) if friction_range is None else friction_range
+            if push_interval:
+                self.push = self._info["push"] = torch.zeros((n_worlds, 6), **f32)
+            if hi > 0:
+                self.friction = self._info["friction"] = torch.full((n_worlds,), float(ground_mu), **f32)
+            rc = N.MwFloatRandConfig(push_interval, push_steps, push_force, push_torque, lo, hi)
+            N.check(N.lib().mw_floatenv_randomize(
+                h, ctypes.byref(rc), None if self.push is None else ctypes.c_void_p(self.push.data_ptr()),
+                None if self.friction is None else ctypes.c_void_p(self.friction.data_ptr())), "mw_floatenv_randomize")
 
     # ------------------------------------------------------------------
     @classmethod
@@ -222,7 +250,7 @@ class FloatVecEnv:
             self._h, ctypes.c_void_p(actions.data_ptr()), ctypes.c_void_p(self.obs.data_ptr()),
             ctypes.c_void_p(self.reward.data_ptr()), ctypes.c_void_p(self.done.data_ptr()),
             ctypes.c_void_p(self.terminal_obs.data_ptr())), "step")
-        return self.obs, self.reward, self.done, {"terminal_obs": self.terminal_obs}
+        return self.obs, self.reward, self.done, dict(self._info)
 
     def step_raw(self, actions_ptr: int) -> None:
         """Launch one step with a raw device pointer (bench / graph capture)."""

@@ -94,6 +94,18 @@ class MwFloatTaskConfig(ctypes.Structure):
     ]
 
 
+class MwFloatRandConfig(ctypes.Structure):
+    """mw_float_rand_config (include/mwstep.h)."""
+    _fields_ = [
+        ("push_interval", ctypes.c_int32),
+        ("push_steps", ctypes.c_int32),
+        ("push_force", ctypes.c_float),
+        ("push_torque", ctypes.c_float),
+        ("friction_lo", ctypes.c_float),
+        ("friction_hi", ctypes.c_float),
+    ]
+
+
 # (name, restype, argtypes) of every symbol in include/mwstep.h
 _P = ctypes.c_void_p
 _I = ctypes.c_int32
@@ -161,6 +173,8 @@ SIGNATURES = [
     ("mw_reset_base_pose", ctypes.c_int, [_P, _I, _I, _D]),
     ("mw_reset_base_velocity", ctypes.c_int, [_P, _I, _I, _D]),
     ("mw_set_ground_plane", ctypes.c_int, [_P, _I, ctypes.c_double]),
+    ("mw_set_ground_friction", ctypes.c_int, [_P, _I, _I, _D]),
+    ("mw_ground_friction", ctypes.c_int, [_P, _I, _I, _D]),
     ("mw_enable_contacts", ctypes.c_int, [_P, _I]),
     ("mw_contacts_enabled", ctypes.c_int, [_P, _IP]),
     ("mw_get_contacts", ctypes.c_int, [_P, _I, _D, _I, _IP]),
@@ -183,6 +197,7 @@ SIGNATURES = [
     ("mw_vecenv_counters", ctypes.c_int, [_P, _P, _P]),
     ("mw_vecenv_physics", ctypes.c_int, [_P, _P, _P]),
     ("mw_floatenv_create", ctypes.c_int, [_P, ctypes.POINTER(MwFloatTaskConfig), ctypes.POINTER(_P)]),
+    ("mw_floatenv_randomize", ctypes.c_int, [_P, ctypes.POINTER(MwFloatRandConfig), _P, _P]),
 ]
 
 # include/mwscene.h

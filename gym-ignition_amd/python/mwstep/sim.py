@@ -254,6 +254,22 @@ class Simulator:
         self._cache.clear()
         N.check(N.lib().mw_set_ground_plane(self.handle, 1 if enabled else 0, float(mu)), "set_ground_plane")
 
+    def set_ground_friction(self, mu, w0: int = 0, nw: Optional[int] = None) -> None:
+        """mw_set_ground_friction: the ground's friction coefficient per world
+        ([nw] or one value for all), from the next run on (world-per-wavefront
+        kernel).  ``set_ground_plane`` still sets every world at once."""
+        self._cache.clear()
+        nw = self.n_worlds - w0 if nw is None else nw
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(mu, dtype=np.float64), (nw,)))
+        N.check(N.lib().mw_set_ground_friction(self.handle, int(w0), int(nw), N.dptr(v)), "set_ground_friction")
+
+    def ground_friction(self, w0: int = 0, nw: Optional[int] = None) -> np.ndarray:
+        """[nw]: the coefficients the next run will use (the kernel's float32 values)."""
+        nw = self.n_worlds - w0 if nw is None else nw
+        out = np.zeros(nw)
+        N.check(N.lib().mw_ground_friction(self.handle, int(w0), int(nw), N.dptr(out)), "ground_friction")
+        return out
+
     def enable_contacts(self, enable: bool = True) -> None:
         self._cache.clear()
         N.check(N.lib().mw_enable_contacts(self.handle, 1 if enable else 0))

@@ -275,6 +275,18 @@ int mw_lcp_solver(const mw_sim* sim, int32_t* mode, int32_t* max_solves);
 int mw_lcp_unconverged(const mw_sim* sim, int64_t* world_steps);
 /* The world's ground plane (z = 0, normal +z) and its friction coefficient. */
 int mw_set_ground_plane(mw_sim* sim, int32_t enabled, double mu);
+/* Per-world friction coefficients of the ground plane, worlds [w0, w0 + nw):
+ * mu[nw] >= 0, used from the next run on (as float32, like the single
+ * coefficient).  Models stepped by the world-per-wavefront kernel only
+ * (mw_float_kernel == 2, generic fixed-base trees); others fail with
+ * MW_ESTATE.  mw_set_ground_plane keeps its meaning: it sets every world to
+ * its mu.  mw_ground_friction returns the values the next run will use; while
+ * a floating-base env randomises the friction (mw_floatenv_randomize) it
+ * reads the env's device copy back, and both setters fail with MW_ESTATE.
+ * Friction is a parameter, not state: mw_get_state / mw_set_state records do
+ * not hold it. */
+int mw_set_ground_friction(mw_sim* sim, int32_t w0, int32_t nw, const double* mu);
+int mw_ground_friction(mw_sim* sim, int32_t w0, int32_t nw, double* mu);
 /* Model::enableContacts / contactsEnabled (Model.cpp:674-700). */
 int mw_enable_contacts(mw_sim* sim, int32_t enable);
 int mw_contacts_enabled(const mw_sim* sim, int32_t* enabled);
@@ -465,6 +477,41 @@ typedef struct {
     const int32_t* contact_links;   /* [n_contact_links] dof index of the link, -1 = base */
 } mw_float_task_config;
 int mw_floatenv_create(mw_sim* sim, const mw_float_task_config* cfg, mw_vecenv** out);
+
+/* Domain randomisation of a floating-base env: pushes on the base and
+ * per-world ground friction, sampled on the device.  Call it after
+ * mw_floatenv_create and before the first mw_vecenv_reset (MW_ESTATE after
+ * it, or on another kind of env).  The step stays three launches without host
+ * copies or synchronisation; the observation layout does not change.
+ * Every draw is Philox4x32-10 keyed by the env's seed with the counter (global
+ * world, episode, block, 0), in blocks the reset draw never reaches:
+ *   episode  block 0x40000000: phase = r[0] % push_interval,
+ *            mu = U(friction_lo, friction_hi) from r[1]; drawn when the
+ *            episode's reset is issued and applied by the run that applies
+ *            the reset (friction randomisation is on when friction_hi > 0)
+ *   pushes   with t the steps already taken in the episode, k = (t + phase) /
+ *            push_interval and o = (t + phase) % push_interval: the step is
+ *            pushed iff o < push_steps, with the world wrench (fx, fy, 0, 0,
+ *            0, tz) on the base link in mw_apply_link_wrench's convention,
+ *            constant over the run's substeps; fx, fy = U(-push_force,
+ *            push_force) from r[0], r[1] and tz = U(-push_torque,
+ *            push_torque) from r[2] of block 0x80000000 | k
+ * U(lo, hi) of a word r is lo + (hi - lo) (r >> 8) 2^-24 in float32.
+ * push_dev float32 [n_worlds, 6] and friction_dev float32 [n_worlds] are
+ * caller-owned device buffers (either may be NULL) that must outlive the env:
+ * every step writes the wrench it applied into push_dev, every reset the new
+ * episode's coefficient into friction_dev.
+ * While an env with pushes exists mw_apply_link_wrench fails with MW_ESTATE
+ * (the wrench buffer is the env's), while one with friction randomisation
+ * exists mw_set_ground_friction and mw_set_ground_plane do. */
+typedef struct {
+    int32_t push_interval;          /* steps between push starts; 0 = no pushes */
+    int32_t push_steps;             /* steps a push lasts, 1..push_interval     */
+    float push_force;               /* N, >= 0                                  */
+    float push_torque;              /* N m, >= 0                                */
+    float friction_lo, friction_hi; /* 0 <= lo <= hi; hi > 0 turns it on        */
+} mw_float_rand_config;
+int mw_floatenv_randomize(mw_vecenv* env, const mw_float_rand_config* cfg, float* push_dev, float* friction_dev);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,11 @@ cost is all they should add; the expectation checked here is
 
   env - bare <= 1.25 x floor.
 
+--randomize adds a fourth graph to the alternation, env_rand: the step of a
+second env with pushes and friction randomisation on (mw_floatenv_randomize;
+the run then takes the wave kernel's wrench path, and the env kernels move 28
+more bytes per world), and reports env_rand - env.
+
 Not a bench.py leg.  Prints one JSON line per model."""
 
 import argparse
@@ -26,6 +31,8 @@ import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# --randomize: a push of 5 steps every 50, and a new friction coefficient per episode
+RANDOMIZE = dict(push_interval=50, push_steps=5, push_force=30.0, push_torque=5.0, friction_range=(0.5, 1.25))
 sys.path.insert(0, os.path.join(ROOT, "gym-ignition_amd", "python"))
 
 
@@ -94,6 +101,13 @@ def measure(torch, args, model, W):
     graphs = {"env": capture(torch, stream, lambda: env.step_raw(actions.data_ptr()), args.warmup),
               "bare": capture(torch, stream, lambda: sim.run_device(1), args.warmup),
               "floor": capture(torch, stream, floor, args.warmup)}
+    rand = None
+    if args.randomize:
+        # a second env with pushes and friction randomisation on, in the same alternation
+        with torch.cuda.stream(stream):
+            rand = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0, **RANDOMIZE)
+            rand.reset()
+        graphs["env_rand"] = capture(torch, stream, lambda: rand.step_raw(actions.data_ptr()), args.warmup)
     times = {k: [] for k in graphs}
     for _ in range(args.rounds):
         for k, g in graphs.items():
@@ -111,6 +125,14 @@ def measure(torch, args, model, W):
            "spread_us": {k: [round(min(v), 3), round(max(v), 3)] for k, v in times.items()},
            "bytes_moved_by_env_kernels": W * (env.obs_dim + env.action_dim) * 4,
            "auto_resets_during_run": done, "base_z_range_after": [round(float(z.min()), 4), round(float(z.max()), 4)]}
+    if rand is not None:
+        pushed = int((rand.push != 0).any(dim=1).sum().item())
+        out.update({"env_rand_step_us": round(med["env_rand"], 3),
+                    "rand_minus_env_us": round(med["env_rand"] - med["env"], 3),
+                    "randomize": RANDOMIZE, "worlds_pushed_in_last_step": pushed,
+                    "friction_range_seen": [round(float(rand.friction.min()), 4), round(float(rand.friction.max()), 4)],
+                    "extra_bytes_per_world": 28})
+        rand.close()
     env.close()
     sim.close()
     return out
@@ -123,6 +145,8 @@ def main():
     p.add_argument("--warmup", type=int, default=50, help="uncaptured calls before each capture")
     p.add_argument("--icub-worlds", type=int, default=512)
     p.add_argument("--quadruped-worlds", type=int, default=4096)
+    p.add_argument("--randomize", action="store_true",
+                   help="also time an env with pushes and friction randomisation on (env_rand)")
     args = p.parse_args()
     if args.replays < 200:
         p.error("--replays must be >= 200")
