@@ -1694,6 +1694,17 @@ int or_float_step_warm(const or_float_model* m, double dt, or_float_state* s, co
                        const double* cmd, int pgs_iters, double pgs_tol, double* warm, double* c_pos,
                        double* c_force, double* c_depth, int32_t* c_body)
 {
+    return or_float_step_ext(m, dt, s, mode, cmd, 0, pgs_iters, pgs_tol, warm, c_pos, c_force, c_depth, c_body);
+}
+
+/* or_float_step_warm with external world wrenches: wrench[1 + OR_MAXB][6],
+ * index 0 the base, then the bodies; [force; torque] in the world frame, the
+ * force acting at the link origin, held over the step (or_scene_step's wrench
+ * input for one model).  NULL: none. */
+int or_float_step_ext(const or_float_model* m, double dt, or_float_state* s, const int32_t* mode,
+                      const double* cmd, const double* wrench, int pgs_iters, double pgs_tol, double* warm,
+                      double* c_pos, double* c_force, double* c_depth, int32_t* c_body)
+{
     const or_model* t = &m->tree;
     const int n = t->n, nv = 6 + n;
     or_fkin k;
@@ -1716,6 +1727,27 @@ int or_float_step_warm(const or_float_model* m, double dt, or_float_state* s, co
         rhs[6 + i] = tau - h[6 + i] - t->damping[i] * s->qd[i];
         Mi[(6 + i) * nv + 6 + i] += dt * t->damping[i];
         nu[6 + i] = s->qd[i];
+    }
+    if (wrench) {
+        for (int b = -1; b < n; ++b) {
+            const double* wr = wrench + (size_t)(b + 1) * 6;
+            if (wr[0] == 0.0 && wr[1] == 0.0 && wr[2] == 0.0 && wr[3] == 0.0 && wr[4] == 0.0 && wr[5] == 0.0)
+                continue;
+            const double* Rl = b < 0 ? s->R : k.Rw[b];
+            /* body-frame spatial force [R^T torque; R^T force] at the link origin */
+            double f[6], Jw[6 + OR_MAXB];
+            for (int r = 0; r < 3; ++r) {
+                f[r] = Rl[r] * wr[3] + Rl[3 + r] * wr[4] + Rl[6 + r] * wr[5];
+                f[3 + r] = Rl[r] * wr[0] + Rl[3 + r] * wr[1] + Rl[6 + r] * wr[2];
+            }
+            if (b < 0) {
+                for (int e = 0; e < nv; ++e) Jw[e] = 0.0;
+                for (int e = 0; e < 6; ++e) Jw[e] = f[e];
+            } else {
+                float_row(m, &k, b, f, Jw);
+            }
+            for (int e = 0; e < nv; ++e) rhs[e] += Jw[e];
+        }
     }
     solve_dense(nv, Mi, rhs, acc);
     for (int e = 0; e < nv; ++e) nu[e] += dt * acc[e];

@@ -208,6 +208,13 @@ int or_float_step(const or_float_model* m, double dt, or_float_state* s, const i
 int or_float_step_warm(const or_float_model* m, double dt, or_float_state* s, const int32_t* mode,
                        const double* cmd, int pgs_iters, double pgs_tol, double* warm, double* c_pos,
                        double* c_force, double* c_depth, int32_t* c_body);
+/* or_float_step_warm with external world wrenches (or_scene_step's wrench
+ * input for one model): wrench[1 + OR_MAXB][6], index 0 the base, then the
+ * bodies; [force; torque] in the world frame, the force acting at the link
+ * origin, held over the step.  NULL: none. */
+int or_float_step_ext(const or_float_model* m, double dt, or_float_state* s, const int32_t* mode,
+                      const double* cmd, const double* wrench, int pgs_iters, double pgs_tol, double* warm,
+                      double* c_pos, double* c_force, double* c_depth, int32_t* c_body);
 
 /* CPU-baseline rollouts under the JointController PID hold (bench.py):
  * W fixed-base worlds (q, qd, q0, PID states [W][n]; targets

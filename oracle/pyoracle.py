@@ -180,6 +180,9 @@ def lib():
         L.or_float_step_warm.argtypes = [FM, ctypes.c_double, FS, I32, D, ctypes.c_int, ctypes.c_double, D, D, D,
                                          D, I32]
         L.or_float_step_warm.restype = ctypes.c_int
+        L.or_float_step_ext.argtypes = [FM, ctypes.c_double, FS, I32, D, D, ctypes.c_int, ctypes.c_double, D, D,
+                                        D, D, I32]
+        L.or_float_step_ext.restype = ctypes.c_int
         L.or_scene_step.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, I32, D, D, ctypes.c_int,
                                     D, I32]
         L.or_scene_step.restype = ctypes.c_int
@@ -1107,6 +1110,9 @@ class FloatWorld:
         self.set_pose(cm.base_p, cm.base_R)
         self.mode = np.zeros(cm.n, dtype=np.int32)
         self.cmd = np.zeros(cm.n)
+        # external world wrenches (or_float_step_ext): [force; torque] at the
+        # link origin, row 0 the base, row 1 + i body i; held until changed
+        self.wrench = np.zeros((1 + OR_MAXB, 6))
         self.contacts = []
 
     def set_pose(self, p, R):
@@ -1156,7 +1162,12 @@ class FloatWorld:
         cmd = self.cmd if cmd is None else np.ascontiguousarray(cmd, dtype=float)
         cp, cf, cd = np.zeros(3 * OR_MAXFC), np.zeros(3 * OR_MAXFC), np.zeros(OR_MAXFC)
         cb = np.zeros(OR_MAXFC, dtype=np.int32)
-        if self.pgs_tol > 0.0 or self.warm is not None:
+        if self.wrench.any():
+            nc = lib().or_float_step_ext(ctypes.byref(self.m), self.dt, ctypes.byref(self.s),
+                                         _p(mode, ctypes.c_int32), _p(cmd), _p(self.wrench), self.pgs,
+                                         self.pgs_tol, _p(self.warm) if self.warm is not None else None,
+                                         _p(cp), _p(cf), _p(cd), _p(cb, ctypes.c_int32))
+        elif self.pgs_tol > 0.0 or self.warm is not None:
             nc = lib().or_float_step_warm(ctypes.byref(self.m), self.dt, ctypes.byref(self.s),
                                           _p(mode, ctypes.c_int32), _p(cmd), self.pgs, self.pgs_tol,
                                           _p(self.warm) if self.warm is not None else None,

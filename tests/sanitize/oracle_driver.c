@@ -71,6 +71,17 @@ int main(int argc, char** argv)
         fwrite(&st, sizeof st, 1, o);
         fwrite(&nc, sizeof nc, 1, o);
         fwrite(cf, sizeof(double), 3 * (size_t)nc, o);
+        /* one more step with world wrenches on the base and the last body
+         * (or_float_step_ext), on the final state; not part of the out file */
+        double* wr = calloc((size_t)(1 + OR_MAXB) * 6, sizeof(double));
+        if (!wr) return 4;
+        for (int e = 0; e < 6; ++e) {
+            wr[e] = 3.0 * (e + 1) * (e % 2 ? -1.0 : 1.0);
+            if (n > 0) wr[(size_t)n * 6 + e] = 0.5 * (6 - e);
+        }
+        if (or_float_step_ext(m, dt, &st, mode, cmd, wr, pgs, 0.0, use_warm ? warm : NULL, cp, cf, cd, cb) < 0)
+            return 5;
+        free(wr);
         free(m); free(warm); free(cp); free(cf); free(cd); free(cb);
     } else {
         return 3;

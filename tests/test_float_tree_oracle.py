@@ -16,7 +16,11 @@ contact / joint rows) is checked against the parts already pinned:
   * the reference's contact KAT transposed to an articulated body
     (tests/test_scenario/test_contacts.py:57-122: the vertical contact forces
     sum to the weight within 0.1 N): the quadruped standing on its four feet
-    under a joint PD hold carries its 16 kg on exactly its feet.
+    under a joint PD hold carries its 16 kg on exactly its feet;
+  * world wrenches (or_float_step_ext, FloatWorld.wrench): against the scene
+    oracle's (or_scene_step) on contact states of the quadruped and the iCub
+    at five friction coefficients from 0 to 1.2, and against p = F t in zero
+    gravity.
 """
 
 import numpy as np
@@ -217,3 +221,103 @@ def test_warm_started_pgs_mode(oracle):
         b.step(mode, tau)
     assert np.mean(sweeps) < 50
     assert np.abs(c.q - b.q).max() <= 1e-4 and np.abs(c.p - b.p).max() <= 1e-5
+
+
+@pytest.mark.parametrize("name, link", [("quadruped", 3), ("icub", 20)])
+def test_world_wrench_matches_the_scene_oracle(oracle, name, link):
+    """or_float_step_ext against or_scene_step (whose wrench input
+    test_gpu_scenario_scene.py pins with v = F t / m) on one model: the
+    contact states of the one-step GPU tests (feet and trunk in the ground,
+    joints beyond their limits, random torques), wrenches on the base and on
+    one other link, the same friction coefficient and the converged solve on
+    both sides.  The two dense formulations differ only in summation order:
+    the state within 1e-9 (measured 2e-15 quadruped, 5e-11 iCub) and the
+    contact forces within 1e-9 of the world's largest contact force,
+    |df| / (1 + max |f|) (measured 7e-16, 1.2e-10).  The iCub's absolute force
+    gap is 3e-8 N, on a 242 N corner force in a world whose largest is 1612 N:
+    its soles' redundant corners make the Delassus matrix conditioned 1.3e8,
+    so how a foot's load splits between its corners is determined to 1e-8
+    relative at best, while the motion is not affected."""
+    from float_oracle_check import quat_to_R, random_states
+    from mwstep import get_model_file
+    W = 24
+    cm = oracle.load_urdf(get_model_file(name))
+    rng = np.random.default_rng(11)
+    q, qd, pose, vel, tau = random_states(cm, W, rng)
+    mus = [0.0, 0.05, 0.3, 0.8, 1.2]
+    worst_state = worst_force = 0.0
+    n_contact = n_pts = 0
+    for w in range(W):
+        wr = {-1: np.concatenate([rng.uniform(-60, 60, 3), rng.uniform(-5, 5, 3)]),
+              link: np.concatenate([rng.uniform(-20, 20, 3), rng.uniform(-2, 2, 3)])}
+        mu = mus[w % 5]
+        fw = oracle.FloatWorld(cm, mu=mu, pgs_iters=oracle.PGS_CONVERGED)
+        sw = oracle.SceneWorld([cm], mu=mu, pgs_iters=oracle.PGS_CONVERGED)
+        # a float32 quaternion is a unit one only to 1e-8: normalised here, since the two
+        # oracles treat a rotation matrix that is not orthonormal differently (a body
+        # point kept in the body frame / taken back with R^T), a 1e-8 effect on the rows
+        R0 = quat_to_R(pose[w, 3:] / np.linalg.norm(pose[w, 3:]))
+        fw.set_pose(pose[w, :3], R0)
+        fw.set_twist(R0.T @ vel[w, 3:], R0.T @ vel[w, :3])
+        fw.set_joints(q[w], qd[w])
+        sw.set_pose(0, pose[w, :3], R0)
+        sw.set_twist(0, R0.T @ vel[w, 3:], R0.T @ vel[w, :3])
+        sw.set_joints(0, q[w], qd[w])
+        for b, f in wr.items():
+            fw.wrench[1 + b] = f
+            sw.wrench[0, 1 + b] = f
+        sw.mode[0, :cm.n] = oracle.FORCE
+        sw.cmd[0, :cm.n] = tau[w]
+        fw.step(np.full(cm.n, oracle.FORCE, np.int32), tau[w])
+        _, res_f = oracle.pgs_stats()
+        sw.step()
+        _, res_s = oracle.pgs_stats()
+        if not (0.0 <= res_f <= 1e-6 and 0.0 <= res_s <= 1e-6):
+            continue   # an exact solve that missed its complementarity conditions is no reference
+        e = max(np.abs(fw.q - sw.q(0)).max(), np.abs(fw.qd - sw.qd(0)).max(), np.abs(fw.V - sw.V(0)).max(),
+                np.abs(fw.p - sw.p(0)).max(), np.abs(fw.R - sw.R(0)).max())
+        worst_state = max(worst_state, float(e))
+        assert len(fw.contacts) == len(sw.contacts)
+        n_contact += len(fw.contacts) > 0
+        f_max = max([float(np.abs(c[1]).max()) for c in fw.contacts], default=0.0)
+        for (p, f, d, b) in fw.contacts:
+            match = [c for c, who in sw.contacts if np.abs(c[:3] - p).max() <= 1e-12 and who[1] == b]
+            assert len(match) == 1
+            worst_force = max(worst_force, float(np.abs(match[0][6:9] - f).max()) / (1.0 + f_max))
+            n_pts += 1
+    print(f"{name}: FloatWorld vs SceneWorld with wrenches, {n_contact}/{W} worlds in contact, {n_pts} points: "
+          f"state {worst_state:.2e}, contact force {worst_force:.2e}")
+    assert n_contact > W // 4
+    assert worst_state <= 1e-9 and worst_force <= 1e-9
+
+
+def test_base_force_gives_linear_momentum(oracle, quad_file):
+    """Zero gravity, no ground, a world force F (and a torque) on the base of
+    the tilted quadruped at rest, joints free.
+      * One step is exact: the scheme solves M (nu' - nu) = dt (f - bias) with
+        the bias zero at rest, so the base rows of M nu', taken to the world
+        frame with the start pose, are dt [torque about the base origin; F].
+      * After t = 0.2 s the world linear momentum is F t up to the first-order
+        drift of the semi-implicit scheme (the base spins and the legs swing:
+        test_momentum_drift_is_first_order): the error falls 10x with a 10x
+        smaller step, and at dt = 1e-4 it is below 1e-4 |F t| (measured
+        1.9e-4 of 6.0 kg m/s; 1.9e-3 at dt = 1e-3)."""
+    cm = oracle.load_urdf(quad_file, pose_xyz=(0.2, -0.1, 1.0), pose_wxyz=(0.9, 0.1, -0.2, 0.3), gravity=(0, 0, 0))
+    F, torque, t = np.array([30.0, -12.0, 7.0]), np.array([1.0, -2.0, 0.5]), 0.2
+    errs = []
+    for dt in (1e-3, 1e-4):
+        fw = oracle.FloatWorld(cm, dt=dt, ground=False)
+        fw.set_joints(np.array([0.3, -0.8] * 4), np.zeros(8))
+        fw.wrench[0] = np.concatenate([F, torque])
+        M0, R0 = fw.dynamics()[0], fw.R
+        fw.step()
+        hb = M0[:6] @ np.concatenate([fw.V, fw.qd])
+        np.testing.assert_allclose(R0 @ hb[3:], F * dt, rtol=0, atol=1e-12)
+        np.testing.assert_allclose(R0 @ hb[:3], torque * dt, rtol=0, atol=1e-12)
+        np.testing.assert_allclose(M0[6:] @ np.concatenate([fw.V, fw.qd]), 0.0, atol=1e-12)   # no joint torque
+        for _ in range(int(round(t / dt)) - 1):
+            fw.step()
+        errs.append(float(np.abs(momentum(fw)[3:] - F * t).max()))
+    print(f"linear momentum after {t} s under a base force: |p - F t| {errs[0]:.2e} (dt 1e-3), {errs[1]:.2e} (dt 1e-4)")
+    assert 7.0 < errs[0] / errs[1] < 13.0
+    assert errs[1] <= 1e-4 * np.abs(F * t).max()

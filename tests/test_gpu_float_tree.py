@@ -25,19 +25,15 @@ import os
 import numpy as np
 import pytest
 
+from float_oracle_check import exact_lcp_acceptance
+from float_oracle_check import quat_to_R as _quat_to_R
+from float_oracle_check import random_states as _random_states
 from test_float_tree_oracle import STAND, chain_urdf
 
 pytestmark = pytest.mark.gpu
 G = 9.8
 # fp32 kernel vs fp64 oracle, one engine step
 TOL = dict(pose=1e-5, q=1e-5, point=1e-5, vel=2e-3, qd=2e-3, force=5e-3)
-
-
-def _quat_to_R(q):
-    w, x, y, z = q
-    return np.array([[1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)],
-                     [2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)],
-                     [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
 
 
 # a branched tree exercising the wave kernel's level-parallel passes: three
@@ -104,28 +100,6 @@ def _model(name):
         write_obj(path, *rock_vertices(6))
         return chain_urdf(int(name[-2]), mesh_tip=path)
     return chain_urdf(int(name[-1]))
-
-
-def _random_states(cm, W, rng):
-    n = cm.n
-    lo = np.array(cm.model.lower[:n])
-    hi = np.array(cm.model.upper[:n])
-    q = rng.uniform(lo, hi, size=(W, n))
-    beyond = rng.uniform(size=(W, n)) < 0.1
-    q[beyond] = np.where(rng.uniform(size=(W, n)) < 0.5, lo - 1e-3, hi + 1e-3)[beyond]
-    qd = rng.uniform(-2, 2, size=(W, n))
-    # base: half the worlds near standing height, half low and tilted
-    axis = rng.normal(size=(W, 3))
-    axis /= np.linalg.norm(axis, axis=1, keepdims=True)
-    ang = rng.uniform(0, 0.5, W)
-    quat = np.column_stack([np.cos(ang / 2), axis * np.sin(ang / 2)[:, None]])
-    z = np.where(np.arange(W) % 2 == 0, rng.uniform(0.30, 0.48, W), rng.uniform(0.02, 0.25, W))
-    pos = np.column_stack([rng.uniform(-1, 1, W), rng.uniform(-1, 1, W), z])
-    lin = rng.uniform(-0.5, 0.5, (W, 3))
-    angv = rng.uniform(-1, 1, (W, 3))
-    tau = rng.uniform(-20, 20, size=(W, n))
-    f32 = lambda a: a.astype(np.float32).astype(np.float64)
-    return f32(q), f32(qd), f32(np.column_stack([pos, quat])), f32(np.column_stack([lin, angv])), f32(tau)
 
 
 @pytest.mark.parametrize("name, kernel", [("quadruped", "lane"), ("chain1", "lane"), ("chain2", "lane"),
@@ -250,7 +224,6 @@ def test_one_step_exact_lcp_random_states(require_gpu, oracle, monkeypatch, name
     had run out of its 24-solve budget at a complementarity error 3,600x
     the tolerance -- the default budget is 48 since, and it converges in
     32).  The agreeing worlds' own backward errors are printed too."""
-    from lcp_validity import contact_set_gap, judge, oracle_ratio, validity
     from mwstep import native as N
     from mwstep.sim import Simulator
     text = _model(name)
@@ -275,49 +248,9 @@ def test_one_step_exact_lcp_random_states(require_gpu, oracle, monkeypatch, name
     sim.run()
     p1, gq1, gqd1 = sim.base_pose(), sim.get("q"), sim.get("qd")
     state = sim.get_state()
-    mode = np.full(cm.n, oracle.FORCE, np.int32)
-
-    no_ref, agree, valid, differ = [], 0, [], []
-    ratios_agree = []
-    for w in range(W):
-        R0 = _quat_to_R(p0[w, 3:])
-        ow = oracle.FloatWorld(cm, ground=True, mu=mu, pgs_iters=oracle.PGS_CONVERGED)
-        ow.set_pose(p0[w, :3], R0)
-        ow.set_twist(R0.T @ v0[w, 3:], R0.T @ v0[w, :3])
-        ow.set_joints(gq0[w], gqd0[w])
-        ow.step(mode, tau[w])
-        _, res = oracle.pgs_stats()
-        if not 0.0 <= res <= 1e-6:
-            no_ref.append(w)
-            continue
-        prob = oracle.lcp_last()
-        e_qd = float(np.abs(gqd1[w] - ow.qd).max())
-        e_q = max(float(np.abs(gq1[w] - ow.q).max()), float(np.abs(p1[w, :3] - ow.p).max()))
-        if e_qd <= 1e-4 and e_q <= 1e-5:
-            agree += 1
-            if prob is not None and not any(contact_set_gap(ow.contacts, sim.contacts(w))):
-                ratios_agree.append(validity(prob, state[w])["ratio"])
-            continue
-        ok, ratio, graze = judge(prob, ow.contacts, sim.contacts(w), state[w])
-        rec = (w, f"{e_qd:.1e}", f"ratio {ratio:.2f}", f"oracle {oracle_ratio(prob) if prob is not None else 0:.2f}",
-               f"grazing {[f'{who} {dep:.1e}' for who, dep in graze]}" if graze else "")
-        if ok and e_q <= 2e-3 * e_qd + 1e-5:
-            valid.append(rec)
-        else:
-            differ.append(rec)
-            if os.environ.get("MW_TEST_DUMP_LCP"):
-                _dump_lcp(dict(prob, gpu_state=state[w]), f"random_{name}_{w}")
-    unconv = sim.lcp_unconverged()
-    n_ref = W - len(no_ref)
-    ra = np.array(ratios_agree) if ratios_agree else np.zeros(1)
-    print(f"exact LCP, random states, {name}: {agree}/{n_ref} worlds agree with the converged oracle "
-          f"(qd <= 1e-4, q / pose <= 1e-5; their GPU impulses' fp64 complementarity / tolerance: "
-          f"median {np.median(ra):.2f}, max {ra.max():.2f}); other valid fp64 solutions {valid}; "
-          f"differ {differ}; oracle unconverged {len(no_ref)}; GPU unconverged {unconv}/{W}")
-    assert sim.constraint_overflow() == 0
-    assert unconv == 0
-    assert not differ
-    assert agree >= 0.85 * n_ref
+    dump = (lambda prob, w: _dump_lcp(prob, f"random_{name}_{w}")) if os.environ.get("MW_TEST_DUMP_LCP") else None
+    exact_lcp_acceptance(sim, oracle, cm, mu, tau, (p0, v0, gq0, gqd0), (p1, gq1, gqd1, state), label=name,
+                         dump=dump)
     sim.close()
 
 
