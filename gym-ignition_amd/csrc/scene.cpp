@@ -531,11 +531,29 @@ int ensure_big(mw_scene* s) {
         mw::pin_ptr<float[]> hc;
         MW_HIP(mw::dev_alloc(dc, n));
         MW_HIP(mw::pin_alloc(hc, n));
+        // the contacts of the last step stay readable (a paused run reports
+        // them again): [cap][12][W] makes the smaller block a prefix of the
+        // larger one.  The device counts stay; the host mirror is stale from
+        // here, so the next read pulls block and counts together (and clamps
+        // the counts to the new capacity, mw_scene_get_contacts).
+        const size_t keep = static_cast<size_t>(std::min(cap, s->contact_cap)) * 12 * s->W * sizeof(float);
+        MW_HIP(hipMemcpyAsync(dc.get(), s->d_contact.get(), keep, hipMemcpyDeviceToDevice, s->stream));
+        if (n > keep)
+            MW_HIP(hipMemsetAsync(reinterpret_cast<uint8_t*>(dc.get()) + keep, 0, n - keep, s->stream));
+        if (cap < s->contact_cap) {
+            // a smaller block: the counts of the last step may exceed it
+            int32_t* hn = s->h_ncontact.get();
+            MW_HIP(hipMemcpyAsync(hn, D.ncontact, s->W * sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+            if (int rc = sync(s)) return rc;
+            for (int w = 0; w < s->W; ++w) hn[w] = std::min(hn[w], cap);
+            MW_HIP(hipMemcpyAsync(D.ncontact, hn, s->W * sizeof(int32_t), hipMemcpyHostToDevice, s->stream));
+        }
+        if (int rc = sync(s)) return rc;   // before the old block is released
         s->d_contact = std::move(dc);
         s->h_contact = std::move(hc);
         s->contact_cap = cap;
+        s->contacts_stale = true;
         D.contact = s->d_contact.get();
-        MW_HIP(hipMemsetAsync(D.ncontact, 0, s->W * sizeof(int32_t), s->stream));
     }
     D.contact_cap = cap;
     return MW_OK;

@@ -891,7 +891,8 @@ struct ScBigWs {
     // row fields: 0 joint-row source (3 body + type, int bits), 1 b, 2 lo, 3
     // hi (the rows' own boxes), 4 stage-1 impulse, 5 / 6 the stage's box, 7
     // active-set state (int bits: 0-1 held at none / lo / hi, 2 frozen, 3
-    // released), 8 gradient A x - b, 9 residual tolerance, 10 LDL^T pivot
+    // released), 8 gradient A x - b (after the step: the joint rows' final
+    // impulses), 9 residual tolerance, 10 LDL^T pivot
     __device__ float* row(int f) const {
         return base + static_cast<size_t>(cmax) * kScBigContactWords + static_cast<size_t>(f) * R;
     }
@@ -1592,6 +1593,8 @@ __device__ __noinline__ ScBigOut sc_big_constraints(const SceneF* __restrict__ P
         L.nu[lane] += dnu;
     }
     for (int r = lane; r < ncr && r < NR; r += kWaveLanes) G.ct(r / 3)[16 + r % 3] = S.xs[r];
+    // the joint rows' impulses next to them (row field 8: the gradient is dead)
+    for (int r = ncr + lane; r < NR; r += kWaveLanes) G.row(8)[r] = S.xs[r];
     __threadfence_block();
     wave_lds_sync();
     return out;

@@ -3012,6 +3012,10 @@ int or_scene_step(const or_scene_model* sm, double dt, or_scene_state* st, const
     static _Thread_local double bb[3 * OR_SC_MAXC + 3 * OR_MAXB], lo[3 * OR_SC_MAXC + 3 * OR_MAXB],
         hi[3 * OR_SC_MAXC + 3 * OR_MAXB], cfm[3 * OR_SC_MAXC + 3 * OR_MAXB], x[3 * OR_SC_MAXC + 3 * OR_MAXB];
     static _Thread_local int kind[3 * OR_SC_MAXC + 3 * OR_MAXB];
+    /* row identities (or_lcp_last_rows): contact rows 3 c + d, joint rows
+     * OR_WARM_JOINT0 + 3 body + type with the scene's body index (the models'
+     * dofs in model order); -1 for a contact beyond OR_WARM_SLOTS */
+    static _Thread_local int rwid[3 * OR_SC_MAXC + 3 * OR_MAXB];
     (void)maxr;
     int nr = 0;
     double tb1[OR_SC_MAXC][3], tb2[OR_SC_MAXC][3];
@@ -3056,14 +3060,16 @@ int or_scene_step(const or_scene_model* sm, double dt, or_scene_state* st, const
             lo[nr] = 0.0;
             hi[nr] = INFINITY;
             cfm[nr] = OR_C_CFM;
+            rwid[nr] = c < OR_WARM_SLOTS ? 3 * c + d : -1;
             ++nr;
         }
     }
-    for (int m = 0; m < K; ++m) {
+    for (int m = 0, body0 = 0; m < K; body0 += sm->model[m].tree.n, ++m) {
         const or_model* t = &sm->model[m].tree;
         const or_float_state* s = &st->s[m];
         for (int i = 0; i < t->n; ++i) {
             const int col = off[m] + nbase[m] + i;
+            const int jw = OR_WARM_JOINT0 + 3 * (body0 + i);
             const double qdi = nu[col];
             int rows_i[3], nri = 0;
             if (t->limited[i]) {
@@ -3079,6 +3085,7 @@ int or_scene_step(const or_scene_model* sm, double dt, or_scene_state* st, const
                     if (bounce > OR_MAX_ERV) bounce = OR_MAX_ERV;
                     if (bounce < -OR_MAX_ERV) bounce = -OR_MAX_ERV;
                     bb[nr] = -qdi + bounce;
+                    rwid[nr] = jw;
                     rows_i[nri++] = nr++;
                 }
             }
@@ -3090,6 +3097,7 @@ int or_scene_step(const or_scene_model* sm, double dt, or_scene_state* st, const
                     bb[nr] = vc - qdi;
                     lo[nr] = -t->effort[i] * dt;
                     hi[nr] = t->effort[i] * dt;
+                    rwid[nr] = jw + 1;
                     rows_i[nri++] = nr++;
                 }
             }
@@ -3097,6 +3105,7 @@ int or_scene_step(const or_scene_model* sm, double dt, or_scene_state* st, const
                 bb[nr] = -qdi;
                 hi[nr] = t->friction[i] * dt;
                 lo[nr] = -hi[nr];
+                rwid[nr] = jw + 2;
                 rows_i[nri++] = nr++;
             }
             for (int r = 0; r < nri; ++r) {
@@ -3125,7 +3134,7 @@ int or_scene_step(const or_scene_model* sm, double dt, or_scene_state* st, const
             for (int r = 0; r < nr; ++r) {
                 for (int c = 0; c < nr; ++c) g_cap_A[r * nr + c] = A[r * nr + c];
                 g_cap_b[r] = bb[r];
-                g_cap_wid[r] = -1;
+                g_cap_wid[r] = rwid[r];
                 g_cap_bscale[r] = fabs(bb[r]);
                 g_cap_x1[r] = 0.0;
                 g_cap_kind[r] = kind[r];

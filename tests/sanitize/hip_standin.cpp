@@ -1,7 +1,8 @@
 // hip_standin.cpp -- a host stand-in for the HIP runtime and the kernel
 // launchers, for the lifecycle harness (lifecycle_driver.cpp).  The runtime
 // entry points the host layer calls work on plain heap memory, so the
-// sanitizers see every buffer, copy and free; launches do nothing.  It counts
+// sanitizers see every buffer, copy and free; launches do nothing (the scene's
+// writes a contact record).  It counts
 // the live objects (buffers, streams, events) and can make one chosen creating
 // call fail, which is how the harness checks what each handle owns.
 #include <hip/hip_runtime.h>
@@ -141,7 +142,26 @@ hipError_t launch_vecenv_step(const ChainF*, int, bool, bool, int, const TaskF&,
                               const void*, float*, float*, uint8_t*, float*, int, float, int, int, int, hipStream_t) {
     return hipSuccess;
 }
-hipError_t launch_scene_run(const SceneF*, int, const SceneDev&, const PidF*, const SceneGates&, int,
-                            const SceneArgs&, hipStream_t) { return hipSuccess; }
+// The one launch that leaves something behind: a step's contact output, so
+// that the host's readback (mw_scene_get_contacts) has records to index --
+// every ground slot of every world touches, node c % n_nodes against the
+// ground, the values numbered.  A paused launch writes nothing, as the kernel.
+hipError_t launch_scene_run(const SceneF* P, int, const SceneDev& D, const PidF*, const SceneGates&, int W,
+                            const SceneArgs& a, hipStream_t) {
+    if (a.paused || !D.contact || !D.ncontact || P->n_nodes <= 0) return hipSuccess;
+    const int slots = P->ground ? P->n_slots : 0;
+    const int nc = slots < D.contact_cap ? slots : D.contact_cap;
+    for (int w = 0; w < W; ++w) {
+        D.ncontact[w] = nc;
+        for (int c = 0; c < nc; ++c) {
+            float* o = D.contact + static_cast<size_t>(c) * 12 * W + w;
+            for (int f = 0; f < 10; ++f) o[static_cast<size_t>(f) * W] = static_cast<float>(100 * w + c + 0.125f * f);
+            const int32_t na = c % P->n_nodes, nb = -1;
+            std::memcpy(o + static_cast<size_t>(10) * W, &na, sizeof na);
+            std::memcpy(o + static_cast<size_t>(11) * W, &nb, sizeof nb);
+        }
+    }
+    return hipSuccess;
+}
 
 }  // namespace mw

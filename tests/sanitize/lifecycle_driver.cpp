@@ -106,6 +106,49 @@ void scene_case(int cubes, Trace& t) {
     mw_scene_destroy(sc);
 }
 
+// Two cubes run, then a third one raises the scene's worst case past the
+// contact output's capacity: the paused run that applies the insertion
+// reallocates the contact block and must report the last step's contacts
+// again -- read before the insertion (the host mirror was current) or not --
+// with every identity a valid index.
+void scene_regrow_case(bool read_before, Trace& t) {
+    mw_scene* sc = nullptr;
+    t.note(mw_scene_create(&kCfg, &sc));
+    const std::string cube = g_models + "/cube.urdf";
+    auto insert = [&](int c) {
+        const double pose[7] = {1.0001 * c, 0, 0.4999, 1, 0, 0, 0};
+        int32_t m = -1;
+        t.note(mw_scene_insert_model(sc, cube.c_str(), pose, ("c" + std::to_string(c)).c_str(), 0, W, &m));
+    };
+    constexpr int kCap = 128, w = W - 1;
+    std::vector<double> before(kCap * 14, -7.0), after(kCap * 14, -7.0);
+    int32_t nb = -1, na = -1;
+    insert(0);
+    insert(1);
+    t.note(mw_scene_set_ground_plane(sc, 1, 0.8));
+    t.note(mw_scene_run(sc, 0));
+    t.note(mw_scene_get_contacts(sc, w, before.data(), kCap, &nb));
+    if (!read_before) {
+        // a second step: the mirror is stale when the block is reallocated
+        t.note(mw_scene_run(sc, 0));
+    }
+    insert(2);
+    if (t.note(mw_scene_run(sc, 1)) != MW_OK) (void)mw_scene_run(sc, 1);   // a failed reallocation is repeated
+    const int rc = t.note(mw_scene_get_contacts(sc, w, after.data(), kCap, &na));
+    if (t.rc == MW_OK && rc == MW_OK) {
+        if (nb != 16 || na != nb) t.bad = "contacts " + std::to_string(nb) + " before and " + std::to_string(na) +
+                                          " after the capacity change (16 expected)";
+        else if (before != after) t.bad = "the paused run after a capacity change reports other contacts";
+        for (int c = 0; c < na && c < kCap; ++c)
+            if (after[c * 14 + 10] < 0 || after[c * 14 + 10] > 2 || after[c * 14 + 12] != -1)
+                t.bad = "a contact names a model that does not exist";
+    }
+    t.note(mw_scene_run(sc, 0));
+    t.note(mw_scene_get_contacts(sc, w, after.data(), kCap, &na));
+    if (t.rc == MW_OK && na != 24) t.bad = "contacts " + std::to_string(na) + " after the step with three cubes (24 expected)";
+    mw_scene_destroy(sc);
+}
+
 void check(const std::string& name, const std::function<void(Trace&)>& run) {
     long leaks = 0;
     auto once = [&](long k, Trace& t) {
@@ -162,5 +205,7 @@ int main(int argc, char** argv) {
     check("scene_create", [](Trace& t) { scene_case(0, t); });
     check("scene_run", [](Trace& t) { scene_case(2, t); });
     check("scene_big", [](Trace& t) { scene_case(8, t); });
+    check("scene_regrow_read", [](Trace& t) { scene_regrow_case(true, t); });
+    check("scene_regrow_stale", [](Trace& t) { scene_regrow_case(false, t); });
     return g_violations ? 1 : 0;
 }

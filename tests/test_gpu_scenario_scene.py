@@ -83,6 +83,8 @@ def test_cube_multiple_contacts(require_gpu, double):
         gazebo.run()
     assert cube1.get_link("cube").in_contact() and cube2.get_link("cube").in_contact()
     assert len(cube1.contacts()) == 1 and len(cube2.contacts()) == 1
+    wrench1 = list(cube1.get_link("cube").contact_wrench())
+    assert wrench1[2] > 0
     assert world.insert_model_from_string(cube_urdf_s, core.Pose([0, 0, 0.301], [1., 0, 0, 0]), "cube3")
     assert len(world.model_names()) == 4
     cube3 = world.get_model("cube3")
@@ -91,6 +93,10 @@ def test_cube_multiple_contacts(require_gpu, double):
     gazebo.run(paused=True)
     assert not cube3.get_link("cube").in_contact()
     assert len(cube3.contacts()) == 0
+    # the insertion raised the scene's contact capacity: the paused run still
+    # reports the last step's contacts of the models that were there
+    assert len(cube1.contacts()) == 1
+    assert list(cube1.get_link("cube").contact_wrench()) == wrench1
     for _ in range(50):
         gazebo.run()
     assert cube3.get_link("cube").in_contact()

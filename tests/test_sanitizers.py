@@ -287,7 +287,11 @@ def test_device_dynamics_on_host_under_sanitizers(san, oracle, panda_file, cartp
 # order have not changed since, so fewer points would mean the driver no longer
 # reaches them.
 LIFECYCLE_POINTS = {"sim_cartpole": 10, "sim_cube": 20, "sim_icub": 20, "env_cartpole": 12, "env_panda": 12,
-                    "scene_create": 21, "scene_run": 21, "scene_big": 24}
+                    "scene_create": 21, "scene_run": 21, "scene_big": 24,
+                    # contact readback across a capacity change (ensure_big: workspace, device and
+                    # pinned contact block), read before the insertion or stale; the driver also
+                    # checks the contacts reported after it
+                    "scene_regrow_read": 24, "scene_regrow_stale": 24}
 
 
 def test_handles_own_their_resources_under_sanitizers(san):
