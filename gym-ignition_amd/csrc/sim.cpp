@@ -1048,6 +1048,7 @@ int run_impl(mw_sim* s, int paused, bool readback) {
     // mirror the kernel's component semantics on the host copy
     std::memset(s->hcmd(), 0, s->nw * sizeof(float));
     std::memset(s->hrflag(), 0, s->nw);
+    s->pid_reset_dofs = 0;
     std::fill(s->cmd64.begin(), s->cmd64.end(), 0.0);
     if (!paused) {
         s->iterations += s->cfg.steps_per_run;
@@ -1463,6 +1464,7 @@ int mw_set_joint_pid(mw_sim* s, int32_t dof, const double gains[8]) {
     if (s->initialized) {
         for (int32_t w = 0; w < s->W; ++w) s->hrflag()[s->idx(dof, w)] |= 4u;
         s->cmd_dirty = true;
+        if (dof < 64) s->pid_reset_dofs |= uint64_t{1} << dof;
     }
     return MW_OK;
 }

@@ -106,6 +106,10 @@ struct mw_sim {
     mw::dev_ptr<mw::PidF[]> d_pid;  // PID gains of every dof (device)
     mw::pin_ptr<mw::PidF[]> h_pid;  // pinned staging copy
     bool pid_dirty = true;        // gains changed since the last upload
+    // dofs whose gains mw_set_joint_pid replaced since the last step (bit per
+    // dof < 64): the position-target env starts their controller state from
+    // zero, as mw_run does through the reset flags
+    uint64_t pid_reset_dofs = 0;
     mw::dev_ptr<int[]> d_overflow;  // constraint rows dropped by the wave kernel
     mw::dev_ptr<float[]> d_warm;  // wave kernel: previous step's PGS impulses [kWaveWarmWordsHost][W]
     double pgs_tol = 0.0;         // mw_set_pgs_options

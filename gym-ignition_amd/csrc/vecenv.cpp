@@ -140,6 +140,7 @@ int mw_vecenv_create(mw_sim* s, const mw_task_config* cfg, mw_vecenv** out) {
         // set last: a failed create leaves the simulator as it was
         s->period_ns = s->dt_ns;
         s->controller = true;
+        s->pid_reset_dofs = 0;  // the controller state is still all zero
     }
     *out = e.release();
     return MW_OK;
@@ -320,6 +321,7 @@ int mw_vecenv_reset(mw_vecenv* e, float* obs) {
     if (e->floatenv) return floatenv_reset(e, obs);
     mw_sim* s = e->sim;
     MW_HIP(mw::launch_vecenv_reset(s->d_params.get(), s->n, e->task, s->dev, e->dev, obs, s->W, s->stream));
+    if (e->task.kind == MW_TASK_PANDA_POSITION_TRACKING) s->pid_reset_dofs = 0;  // the reset zeroed every PID
     s->host_stale = true;
     return MW_OK;
 }
@@ -336,6 +338,26 @@ static int vec_common(mw_vecenv* e, int32_t T, const void* a, float* o, float* r
     mw_sim* s = e->sim;
     if (e->task.kind == MW_TASK_PANDA_POSITION_TRACKING) {
         if (T > 0) return fail(MW_EINVAL, "the fused rollout is not available for position-target tasks");
+        if (s->pid_reset_dofs) {
+            // Joint::setPID stores a new ignition::math::PID (Joint.cpp:479-525):
+            // the controller of a dof whose gains changed since the last step
+            // starts from a reset state.  mw_run does this through the reset
+            // flags, which the env kernels do not read.
+            hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+            MW_HIP(hipStreamIsCapturing(s->stream, &cap));
+            if (cap != hipStreamCaptureStatusNone)
+                return fail(MW_ESTATE, "a PID reset after mw_set_joint_pid cannot be captured into a graph: "
+                                       "step once before capturing");
+            const size_t row = static_cast<size_t>(s->W) * sizeof(float);
+            for (int d = 0; d < s->n && d < 64; ++d) {
+                if (!((s->pid_reset_dofs >> d) & 1u)) continue;
+                MW_HIP(hipMemsetAsync(s->dev.pid_e + static_cast<size_t>(d) * s->W, 0, row, s->stream));
+                MW_HIP(hipMemsetAsync(s->dev.pid_i + static_cast<size_t>(d) * s->W, 0, row, s->stream));
+                MW_HIP(hipMemsetAsync(s->dev.pid_u + static_cast<size_t>(d) * s->W, 0, row, s->stream));
+                for (int32_t w = 0; w < s->W; ++w) s->hrflag()[s->idx(d, w)] &= static_cast<uint8_t>(~4u);
+            }
+            s->pid_reset_dofs = 0;
+        }
         // one world per 16-lane row (group_kernel.hip) unless
         // MWSTEP_PANDA_KERNEL=lane asks for the one-world-per-lane kernel
         const char* kk = std::getenv("MWSTEP_PANDA_KERNEL");

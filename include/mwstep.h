@@ -362,8 +362,9 @@ int mw_set_state(mw_sim* sim, int32_t w0, int32_t nw, const float* in);
 #define MW_TASK_PENDULUM_SWINGUP 3
 /* Position-target control of the 9-dof Panda (BASELINE config 4): actions
  * float32 [n_worlds, 9] are the Position-mode targets of every joint, the
- * JointController PID (gains: mw_set_joint_pid) runs every physics step;
- * obs = [q, qd] (18), reward = -|q - target|^2, done = TimeLimit only; reset
+ * JointController PID (gains: mw_set_joint_pid; called between steps, the
+ * next step starts that dof's controller from a reset state in every world)
+ * runs every physics step; obs = [q, qd] (18), reward = -|q - target|^2, done = TimeLimit only; reset
  * to the Panda wrapper's pose (python/gym_ignition_environments/models/
  * panda.py:41-44) with joints 1 and 6 at mid-range (test_pid_controllers.py:
  * 49-59) and the fingers half open, + U(-0.05, 0.05) per joint. */

@@ -876,6 +876,13 @@ int or_step(const or_model* m, double dt, double* q, double* qd,
             const int32_t* mode, const double* cmd, int pgs_iters,
             double* qdd_out, double* force_out)
 {
+    return or_step_rows(m, dt, q, qd, mode, cmd, pgs_iters, qdd_out, force_out, 0, 0);
+}
+
+int or_step_rows(const or_model* m, double dt, double* q, double* qd,
+                 const int32_t* mode, const double* cmd, int pgs_iters,
+                 double* qdd_out, double* force_out, int32_t* limit_row, int32_t* friction_row)
+{
     const int n = m->n;
     double tau[OR_MAXB] = {0}, qdd[OR_MAXB] = {0};
     or_impulse_factor fac;
@@ -895,7 +902,11 @@ int or_step(const or_model* m, double dt, double* q, double* qd,
     for (int i = 0; i < n; ++i) qd[i] += dt * qdd[i];
 
     /* constraint rows: limit, servo, Coulomb friction (per joint, body order) */
-    int rd[3 * OR_MAXB];
+    int rd[3 * OR_MAXB], kind[3 * OR_MAXB];  /* kind: 0 limit, 1 servo, 2 friction */
+    for (int i = 0; i < n; ++i) {
+        if (limit_row) limit_row[i] = OR_ROW_NONE;
+        if (friction_row) friction_row[i] = OR_ROW_NONE;
+    }
     double b[3 * OR_MAXB], lo[3 * OR_MAXB], hi[3 * OR_MAXB];
     int nr = 0;
     for (int i = 0; i < n; ++i) {
@@ -912,6 +923,7 @@ int or_step(const or_model* m, double dt, double* q, double* qd,
                 if (bounce > OR_MAX_ERV) bounce = OR_MAX_ERV;
                 if (bounce < -OR_MAX_ERV) bounce = -OR_MAX_ERV;
                 b[nr] = -qd[i] + bounce;
+                kind[nr] = 0;
                 rd[nr++] = i;
             }
         }
@@ -924,6 +936,7 @@ int or_step(const or_model* m, double dt, double* q, double* qd,
                 b[nr] = err;
                 lo[nr] = -m->effort[i] * dt;
                 hi[nr] = m->effort[i] * dt;
+                kind[nr] = 1;
                 rd[nr++] = i;
             }
         }
@@ -931,6 +944,7 @@ int or_step(const or_model* m, double dt, double* q, double* qd,
             b[nr] = -qd[i];
             hi[nr] = m->friction[i] * dt;
             lo[nr] = -hi[nr];
+            kind[nr] = 2;
             rd[nr++] = i;
         }
     }
@@ -952,6 +966,11 @@ int or_step(const or_model* m, double dt, double* q, double* qd,
         }
         or_pgs(nr, A, b, lo, hi, x, pgs_iters);
         for (int r = 0; r < nr; ++r) imp[rd[r]] += x[r];
+        for (int r = 0; r < nr; ++r) {
+            if (kind[r] == 0 && limit_row) limit_row[rd[r]] = isinf(hi[r]) ? OR_ROW_LOWER : OR_ROW_UPPER;
+            if (kind[r] == 2 && friction_row)
+                friction_row[rd[r]] = (x[r] > lo[r] && x[r] < hi[r]) ? OR_ROW_STICK : OR_ROW_SLIDE;
+        }
         double dqd[OR_MAXB];
         for (int i = 0; i < n; ++i) dqd[i] = 0.0;
         for (int i = 0; i < n; ++i)

@@ -80,6 +80,17 @@ int or_step(const or_model* m, double dt, double* q, double* qd,
             const int32_t* mode, const double* cmd, int pgs_iters,
             double* qdd_out, double* force_out);
 
+/* or_step, which also reports the rows of every dof (either array may be 0):
+ *   limit_row[i]     OR_ROW_NONE / OR_ROW_LOWER / OR_ROW_UPPER
+ *   friction_row[i]  OR_ROW_NONE (no Coulomb friction, or the velocity after
+ *                    the unconstrained update is exactly 0), OR_ROW_STICK (the
+ *                    impulse ends strictly inside +-friction dt), OR_ROW_SLIDE
+ *                    (on a bound of the box) */
+enum { OR_ROW_NONE = 0, OR_ROW_LOWER = 1, OR_ROW_UPPER = 2, OR_ROW_STICK = 3, OR_ROW_SLIDE = 4 };
+int or_step_rows(const or_model* m, double dt, double* q, double* qd,
+                 const int32_t* mode, const double* cmd, int pgs_iters,
+                 double* qdd_out, double* force_out, int32_t* limit_row, int32_t* friction_row);
+
 /* Boxed LCP by projected Gauss-Seidel (A row-major n*n).  Every solver of
  * this oracle takes a sweep budget: iters >= 0 runs exactly that many sweeps
  * (the GPU kernels' count); iters < 0 (OR_PGS_CONVERGED) sweeps to the fixed

@@ -170,6 +170,8 @@ def lib():
         L.or_rnea.argtypes = [M, D, D, D, D]
         L.or_step.argtypes = [M, ctypes.c_double, D, D, I32, D, ctypes.c_int, D, D]
         L.or_step.restype = ctypes.c_int
+        L.or_step_rows.argtypes = [M, ctypes.c_double, D, D, I32, D, ctypes.c_int, D, D, I32, I32]
+        L.or_step_rows.restype = ctypes.c_int
         L.or_pgs.argtypes = [ctypes.c_int, D, D, D, D, D, ctypes.c_int]
         L.or_free_step.argtypes = [ctypes.POINTER(OrFreeModel), ctypes.c_double, ctypes.POINTER(OrFreeState),
                                    ctypes.c_int, D, D, D, D]
@@ -890,6 +892,26 @@ def step(cm: ChainModel, dt, q, qd, mode, cmd, pgs_iters=50):
     return q, qd, qdd, f, nr
 
 
+ROW_NONE, ROW_LOWER, ROW_UPPER, ROW_STICK, ROW_SLIDE = 0, 1, 2, 3, 4
+
+
+def step_rows(cm: ChainModel, dt, q, qd, mode, cmd, pgs_iters=50):
+    """step() that also reports the rows per dof: returns (q, qd, limit_row,
+    friction_row) with limit_row in ROW_NONE / ROW_LOWER / ROW_UPPER and
+    friction_row in ROW_NONE (no friction, or qd exactly 0 after the
+    unconstrained update) / ROW_STICK (strictly inside the box) / ROW_SLIDE
+    (on its bound)."""
+    q = np.array(q, dtype=np.float64)
+    qd = np.array(qd, dtype=np.float64)
+    mode = np.ascontiguousarray(mode, dtype=np.int32)
+    cmd = np.ascontiguousarray(cmd, dtype=np.float64)
+    lim = np.zeros(cm.n, dtype=np.int32)
+    fric = np.zeros(cm.n, dtype=np.int32)
+    lib().or_step_rows(ctypes.byref(cm.model), dt, _p(q), _p(qd), _p(mode, ctypes.c_int32), _p(cmd), pgs_iters,
+                       None, None, _p(lim, ctypes.c_int32), _p(fric, ctypes.c_int32))
+    return q, qd, lim, fric
+
+
 # scenario::core::PID defaults (cpp/scenario/core/include/scenario/core/utils/
 # utils.h PID struct): cmd / integral limits open; Joint.cpp:63 DefaultPID is
 # ignition::math::PID(1, 0.1, 0.01, -1, 0, -1, 0, 0) (empty ranges: no clamp).
@@ -989,11 +1011,15 @@ class ScenarioWorld:
             for d in range(n):
                 m = self.mode[d]
                 if m in (POSITION, VELOCITY):
+                    # a skipped update re-applies PID::Cmd(); a computed one
+                    # applies what Update() returns (JointController.cpp:308-315),
+                    # which is 0 with the state untouched for a non-finite error
+                    u = self.state[d].cmd
                     if compute:
                         cur = self.q[d] if m == POSITION else self.qd[d]
                         tgt = self.ptgt[d] if m == POSITION else self.vtgt[d]
-                        pid_update(self.gains[d], self.state[d], cur - tgt, self.dt)
-                    mode[d], cmd[d] = FORCE, self.state[d].cmd
+                        u = pid_update(self.gains[d], self.state[d], cur - tgt, self.dt)
+                    mode[d], cmd[d] = FORCE, u
                 elif m == VELOCITY_FOLLOWER_DART:
                     mode[d], cmd[d] = SERVO, self.vtgt[d]
                 elif m == FORCE_MODE:

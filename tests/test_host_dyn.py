@@ -16,18 +16,31 @@ HARNESS = os.path.join(ROOT, "tests", "host_dyn", "harness.cpp")
 CSRC = os.path.join(ROOT, "gym-ignition_amd", "csrc")
 
 
+_harness = None
+
+
+def build_harness():
+    """The harness library, compiled once per session (also used by
+    tests/test_panda_cases.py)."""
+    global _harness
+    if _harness is None:
+        import tempfile
+        out = os.path.join(tempfile.mkdtemp(prefix="hd"), "libhd.so")
+        # -DMW_FAST_MATH: the device's Cody-Waite sincos is exercised on the host too
+        subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-DMW_FAST_MATH", "-I", CSRC,
+                        HARNESS, "-o", out], check=True)
+        L = ctypes.CDLL(out)
+        L.hd_substep.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_float, ctypes.c_int, ctypes.c_int,
+                                                          ctypes.c_int, ctypes.c_void_p]
+        L.hd_float_step.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_float, ctypes.c_int, ctypes.c_int,
+                                                             ctypes.c_void_p, ctypes.c_void_p]
+        _harness = L
+    return _harness
+
+
 @pytest.fixture(scope="module")
-def hd(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("hd") / "libhd.so")
-    # -DMW_FAST_MATH: the device's Cody-Waite sincos is exercised on the host too
-    subprocess.run(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-DMW_FAST_MATH", "-I", CSRC,
-                    HARNESS, "-o", out], check=True)
-    L = ctypes.CDLL(out)
-    L.hd_substep.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_float, ctypes.c_int, ctypes.c_int,
-                                                      ctypes.c_int, ctypes.c_void_p]
-    L.hd_float_step.argtypes = [ctypes.c_void_p] * 6 + [ctypes.c_float, ctypes.c_int, ctypes.c_int,
-                                                         ctypes.c_void_p, ctypes.c_void_p]
-    return L
+def hd():
+    return build_harness()
 
 
 def _params(hd, path, joint_params=()):
@@ -137,6 +150,33 @@ def test_panda_tree_with_limit_rows(hd, oracle, panda_file):
                           tau.astype(float), 30)
         worst = max(worst, float(np.abs(got[1] - ref[1]).max()))
     assert worst <= 2e-4, worst
+
+
+@pytest.mark.parametrize("name", ["damped", "frictional", "both", "free", "partial"])
+def test_panda_tree_damped_frictional(hd, oracle, panda_file, name):
+    """The Panda tree on the variants of tests/panda_cases.py at the one-step
+    states of the GPU tests (a fifth of the joints 2 mrad beyond a limit, 30 %
+    of the velocities inside +-2e-3), constant forces, 20 sweeps: the second
+    impulse factor (dual=True: M^-1 columns without the dt D diagonal),
+    friction rows beside limit rows, and the unconstrained path with implicit
+    damping (`free`), float32 device code vs the fp64 oracle.
+    Measured max|dqd|: damped 5.4e-7, frictional 6.0e-7, both 4.7e-7, free
+    1.1e-7; max|dq| 1.2e-7 on all four (half an ulp of a float32 q near 2)."""
+    import panda_cases as pc
+    model, params, cm = pc.variant(oracle, name)
+    P = _params(hd, model, [(d, which, v) for (d, which), v in params.items()])
+    cons, dual = name != "free", name != "frictional"
+    z = np.zeros(9)
+    worst_q = worst_qd = 0.0
+    for seed in (21, 22, 23, 24):
+        q, qd, _ = pc.step_states(oracle, 64, seed)
+        for w in range(len(q)):
+            got = _substep(hd, P, q[w], qd[w], pc.TAU, z, z, cons=cons, dual=dual)
+            ref = oracle.step(cm, 1e-3, q[w].astype(float), qd[w].astype(float), [oracle.FORCE] * 9, pc.TAU, 20)
+            worst_q = max(worst_q, float(np.abs(got[0] - ref[0]).max()))
+            worst_qd = max(worst_qd, float(np.abs(got[1] - ref[1]).max()))
+    print(f"host harness, {name}: max|dq| {worst_q:.2e}, max|dqd| {worst_qd:.2e}")
+    assert worst_qd <= 2e-4 and worst_q <= 1e-5, (worst_q, worst_qd)
 
 
 def _float_blocks(hd, text, mu):
