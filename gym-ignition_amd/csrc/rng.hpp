@@ -26,6 +26,13 @@ __device__ __forceinline__ void philox(uint32_t seed_lo, uint32_t seed_hi, uint3
 __device__ __forceinline__ float unif(uint32_t x, float lo, float hi) {
     return lo + (hi - lo) * (static_cast<float>(x >> 8) * (1.f / 16777216.f));
 }
+// unif() of constant bounds with the exact power-of-two scale folded into the
+// slope: (hi - lo) * 2^-24 and x * 2^-24 are both exact (no underflow: the
+// slope is a normal number), so the product is the same real number and the
+// contracted fma rounds it once, as in unif().  Bit-identical, one multiply less.
+__device__ __forceinline__ float unif_folded(uint32_t x, float lo, float hi) {
+    return lo + ((hi - lo) * (1.f / 16777216.f)) * static_cast<float>(x >> 8);
+}
 
 }  // namespace dev
 }  // namespace mw

@@ -11,6 +11,7 @@
 // global loads wait on no kernarg round trip.  The step kernel
 // therefore takes flat arguments and one compact by-value block (VecArgs)
 // instead of the TaskF / SimDev / VecDev structs.
+#include <cstdlib>
 #include <type_traits>
 
 #include "baked_models.hpp"
@@ -87,11 +88,16 @@ constexpr float kPi = 3.14159265358979323846f;
 // ----------------------------------------------------------- tasks ------
 // kinds: 0 CartPoleDiscreteBalancing, 1 CartPoleContinuousBalancing,
 //        2 CartPoleContinuousSwingup, 3 PendulumSwingUp
-template <int N, int KIND, class TT>
+// FOLD (the helper wave's draw): rng.hpp's unif_folded, the same bits.
+template <int N, int KIND, bool FOLD = false, class TT>
 __device__ __forceinline__ void task_reset(const TT& T, uint32_t w, uint32_t episode,
                                            float (&q)[N], float (&qd)[N]) {
     uint32_t r[4];
     philox(T.seed_lo, T.seed_hi, w, episode, r);
+    const auto unif = [](uint32_t x, float lo, float hi) {
+        if constexpr (FOLD) return unif_folded(x, lo, hi);
+        else return dev::unif(x, lo, hi);
+    };
     if constexpr (KIND == 0 || KIND == 1) {
         // x, dx, q, dq = U(-0.05, 0.05)   cartpole_discrete_balancing.py:137
         q[0] = unif(r[0], -0.05f, 0.05f); qd[0] = unif(r[1], -0.05f, 0.05f);
@@ -120,14 +126,20 @@ __device__ __forceinline__ void task_obs(const float (&q)[N], const float (&qd)[
     }
 }
 
-template <int KIND, class TT>
+// ABS (the HELP kernels): |o| <= hi in place of -hi <= o <= hi, half the
+// compares.  The same boolean for every finite o and either sign of hi
+// (hi < 0: both say "outside"); the kernels are built finite-math-only.
+template <int KIND, bool ABS = false, class TT>
 __device__ __forceinline__ bool task_done(const TT& T, const float (&o)[4]) {
     constexpr int no = (KIND == 3) ? 3 : 4;
     // every comparison evaluated, combined bitwise: the same boolean as the
     // short-circuit form without its nested exec-mask branches
     bool inside = true;
 #pragma unroll
-    for (int k = 0; k < no; ++k) inside = inside & (o[k] >= -T.hi[k]) & (o[k] <= T.hi[k]);
+    for (int k = 0; k < no; ++k) {
+        if constexpr (ABS) inside = inside & (fabsf(o[k]) <= T.hi[k]);
+        else inside = inside & (o[k] >= -T.hi[k]) & (o[k] <= T.hi[k]);
+    }
     return !inside;
 }
 
@@ -211,13 +223,39 @@ __device__ __forceinline__ void store_dyn(const TT& T, const VV& V, int W, int w
     if (T.randomize & kRandGravity) V.rgz[w] = gz;
 }
 
-template <int N>
+// Element i of a uniform array.  OFF32 (the HELP kernels, W <= 16384 worlds):
+// one unsigned 32-bit byte offset added to the uniform pointer, which the
+// compiler emits as the scalar-base form `global_load_dword v, v_off, s[b:b+1]`
+// with no 64-bit vector address arithmetic.  A row d > 0 goes into i (d * W
+// + w), never into the pointer.  Otherwise the plain index, as written.
+template <bool OFF32, class E, class I>
+__device__ __forceinline__ E* elem(E* base, I i) {
+    if constexpr (OFF32) {
+        using Byte = std::conditional_t<std::is_const_v<E>, const char, char>;
+        return reinterpret_cast<E*>(reinterpret_cast<Byte*>(base) +
+                                    static_cast<uint32_t>(i) * static_cast<uint32_t>(sizeof(E)));
+    } else {
+        return base + i;
+    }
+}
+
+// The world index as a value of the basic block that calls this.  The
+// compiler otherwise reuses the 64-bit addresses of the loads at the top for
+// the stores of another block, and builds them with vector 64-bit adds; an
+// offset computed in the store's own block folds into the scalar-base form.
+// Emits no instruction.
+__device__ __forceinline__ int own_block(int w) {
+    asm volatile("" : "+v"(w));
+    return w;
+}
+
+template <int N, bool OFF32 = false>
 __device__ __forceinline__ void store_state(float* __restrict__ sq, float* __restrict__ sqd, int W, int w,
                                             const float (&q)[N], const float (&qd)[N]) {
 #pragma unroll
     for (int d = 0; d < N; ++d) {
-        sq[d * W + w] = q[d];
-        sqd[d * W + w] = qd[d];
+        *elem<OFF32>(sq, d * W + w) = q[d];
+        *elem<OFF32>(sqd, d * W + w) = qd[d];
     }
 }
 
@@ -266,13 +304,26 @@ __global__ void __launch_bounds__(256) vecenv_reset_kernel(const ChainF* __restr
 // first store, and a done lane reads its reset state from LDS instead of
 // running Philox behind the physics.  Every thread reaches the barrier: there
 // is no early return, lanes past W work on world W - 1 and store nothing.
-template <int N, int KIND, bool DUAL, bool CONS, bool ROLLOUT, int BAKED, bool RAND, int B, bool HELP = false>
+// The HELP kernels address every array by a 32-bit byte offset (elem above);
+// they run at W <= kHelpMaxWorlds.
+//
+// ONE (HELP kernels only): the engine substep as straight-line code for
+// substeps == 1, chosen by the launcher; `substeps` is then not read.  The
+// same arithmetic as one trip of the loop, without the loop's phi copies,
+// counter and force select, and with the limit rows' setup inside their branch.
+constexpr int kHelpMaxWorlds = 64 * 256;
+template <int N, int KIND, bool DUAL, bool CONS, bool ROLLOUT, int BAKED, bool RAND, int B, bool HELP = false,
+          bool ONE = false>
 __global__ void __launch_bounds__(256) vecenv_step_kernel(float* __restrict__ sq, float* __restrict__ sqd,
                                                           uint32_t* __restrict__ ep, uint32_t* __restrict__ st,
                                                           const void* __restrict__ actions, int W, float dt,
                                                           int substeps, int pgs_iters,
                                                           VecArgs<RAND, BAKED == 0> A) {
     static_assert(!HELP || (B == 64 && !ROLLOUT && !RAND), "the helper wave serves the closed-loop 64-world blocks");
+    static_assert(!ONE || HELP, "the single-substep form exists for the helper-wave kernels");
+    // the largest byte offset of a HELP kernel: a float4 row of obs / term_obs
+    static_assert(static_cast<uint64_t>(kHelpMaxWorlds) * (N > 4 ? N : 4) * sizeof(float) < (1ull << 32),
+                  "32-bit byte offsets cover every array of the HELP kernels");
     __shared__ float reset_lds[HELP ? 2 * N * B : 1];   // [component][lane]
     const int lane = HELP ? static_cast<int>(threadIdx.x) & (B - 1) : static_cast<int>(threadIdx.x);
     int w = blockIdx.x * B + lane;
@@ -288,14 +339,14 @@ __global__ void __launch_bounds__(256) vecenv_step_kernel(float* __restrict__ sq
     float q[N], qd[N];
 #pragma unroll
     for (int d = 0; d < N; ++d) {
-        q[d] = sq[d * W + w];
-        qd[d] = sqd[d * W + w];
+        q[d] = *elem<HELP>(sq, d * W + w);
+        qd[d] = *elem<HELP>(sqd, d * W + w);
     }
-    const uint32_t episode0 = ep[w];
+    const uint32_t episode0 = *elem<HELP>(ep, w);
     uint32_t episode = episode0;
-    uint32_t steps = st[w];
+    uint32_t steps = *elem<HELP>(st, w);
     ActT a0 = ActT(0);
-    if constexpr (!ROLLOUT) a0 = static_cast<const ActT*>(actions)[w];
+    if constexpr (!ROLLOUT) a0 = *elem<HELP>(static_cast<const ActT*>(actions), w);
     fetch_now(A);
     float* __restrict__ obs = A.obs;
     float* __restrict__ reward = A.reward;
@@ -316,7 +367,7 @@ __global__ void __launch_bounds__(256) vecenv_step_kernel(float* __restrict__ sq
         // instructions with no scalar wait in front of them
         if (__builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x)) >= B) {
             float rq[N], rqd[N];
-            task_reset<N, KIND>(A, A.world_offset + static_cast<uint32_t>(w), episode0 + 1u, rq, rqd);
+            task_reset<N, KIND, true>(A, A.world_offset + static_cast<uint32_t>(w), episode0 + 1u, rq, rqd);
 #pragma unroll
             for (int d = 0; d < N; ++d) {
                 reset_lds[d * B + lane] = rq[d];
@@ -332,6 +383,7 @@ __global__ void __launch_bounds__(256) vecenv_step_kernel(float* __restrict__ sq
             return;
         }
     }
+    int ws = w;   // HELP: the world index of the final stores' block (own_block)
     const int nsteps = ROLLOUT ? A.T_steps : 1;
     for (int t = 0; t < nsteps; ++t) {
         const size_t idx = static_cast<size_t>(t) * W + w;
@@ -347,12 +399,19 @@ __global__ void __launch_bounds__(256) vecenv_step_kernel(float* __restrict__ sq
         const float e = P->b[0].effort;
         force = fminf(fmaxf(force, -e), e);
         float tau[N], qdd[N];
-        for (int s = 0; s < substeps; ++s) {
+        if constexpr (ONE) {
 #pragma unroll
             for (int d = 0; d < N; ++d) tau[d] = 0.f;
-            tau[0] = (s == 0) ? force : 0.f;
-            if constexpr (RAND) substep_dyn<N, DUAL, CONS>(P, q, qd, tau, act, vc, dt, pgs_iters, qdd, D);
-            else substep<N, DUAL, CONS>(P, q, qd, tau, act, vc, dt, pgs_iters, qdd);
+            tau[0] = force;
+            substep<N, DUAL, CONS>(P, q, qd, tau, act, vc, dt, pgs_iters, qdd);
+        } else {
+            for (int s = 0; s < substeps; ++s) {
+#pragma unroll
+                for (int d = 0; d < N; ++d) tau[d] = 0.f;
+                tau[0] = (s == 0) ? force : 0.f;
+                if constexpr (RAND) substep_dyn<N, DUAL, CONS>(P, q, qd, tau, act, vc, dt, pgs_iters, qdd, D);
+                else substep<N, DUAL, CONS>(P, q, qd, tau, act, vc, dt, pgs_iters, qdd);
+            }
         }
         // an unconditional use of the action: its load stays with the state
         // loads above instead of sinking under the `substeps > 0` branch,
@@ -362,7 +421,7 @@ __global__ void __launch_bounds__(256) vecenv_step_kernel(float* __restrict__ sq
         if constexpr (!ROLLOUT) asm volatile("" ::"v"(a0));
         float o[4];
         task_obs<N, KIND>(q, qd, o);
-        const bool tdone = task_done<KIND>(A, o);
+        const bool tdone = task_done<KIND, HELP>(A, o);
         const float rew = task_reward<N, KIND>(A, q, qd, o, tdone);
         if constexpr (!HELP) reward[idx] = rew;
         steps += 1u;
@@ -372,11 +431,13 @@ __global__ void __launch_bounds__(256) vecenv_step_kernel(float* __restrict__ sq
             // store has been issued yet, so the barrier waits on LDS only
             __syncthreads();
             if (!live) return;
-            reward[idx] = rew;
+            *elem<HELP>(reward, idx) = rew;
         }
-        done_out[idx] = d_ ? 1 : 0;
+        if constexpr (HELP) *elem<true>(done_out, idx) = d_ ? 1 : 0;
+        else done_out[idx] = d_ ? 1 : 0;
         if (d_) {
-            store_obs<NO>(term_obs + idx * NO, o);
+            if constexpr (HELP) store_obs<NO>(elem<true>(term_obs, own_block(w) * NO), o);
+            else store_obs<NO>(term_obs + idx * NO, o);
             episode += 1u;
             steps = 0u;
             if constexpr (RAND) {
@@ -396,11 +457,22 @@ __global__ void __launch_bounds__(256) vecenv_step_kernel(float* __restrict__ sq
             }
             task_obs<N, KIND>(q, qd, o);
         }
-        store_obs<NO>(obs + idx * NO, o);
+        if constexpr (HELP) {
+            ws = own_block(w);
+            store_obs<NO>(elem<true>(obs, ws * NO), o);
+        } else {
+            store_obs<NO>(obs + idx * NO, o);
+        }
     }
-    store_state<N>(sq, sqd, W, w, q, qd);
-    if (episode != episode0) ep[w] = episode;  // changes only on auto-reset
-    st[w] = steps;
+    store_state<N, HELP>(sq, sqd, W, ws, q, qd);
+    if constexpr (HELP) {
+        // the unconditional stores in one block; the rare one behind them
+        *elem<true>(st, ws) = steps;
+        if (episode != episode0) *elem<true>(ep, own_block(ws)) = episode;   // changes only on auto-reset
+    } else {
+        if (episode != episode0) ep[w] = episode;  // changes only on auto-reset
+        st[w] = steps;
+    }
 }
 
 }  // namespace dev
@@ -412,7 +484,14 @@ dim3 grid_for(int W, int block) { return dim3(static_cast<unsigned>((W + block -
 
 // 64-thread blocks spread a small world count over as many CUs as possible
 // (each wave runs a long dependent chain); 256 once there is work for all.
-int block_for(int W) { return (W <= 64 * 256) ? 64 : 256; }
+int block_for(int W) { return (W <= dev::kHelpMaxWorlds) ? 64 : 256; }
+
+// MWSTEP_FORCE_SUBSTEP_LOOP=1 keeps the loop instantiation at substeps == 1
+// (the A/B and the bit-equality test of the single-substep kernels).
+bool substep_loop_forced() {
+    const char* v = std::getenv("MWSTEP_FORCE_SUBSTEP_LOOP");
+    return v && *v && *v != '0';
+}
 
 struct StepCall {
     const ChainF* P;
@@ -462,7 +541,12 @@ hipError_t vec_launch(const StepCall& c) {
     // inline) and the 256-thread path, where doubled waves would cost
     // throughput, keep the inline reset
     constexpr bool HELP = !ROLLOUT && !RAND;
-    if (block_for(W) == 64)
+    if (HELP && block_for(W) == 64 && c.substeps == 1 && !substep_loop_forced())
+        // one substep: the straight-line instantiation (the kernel's ONE)
+        hipLaunchKernelGGL((dev::vecenv_step_kernel<N, KIND, DUAL, CONS, ROLLOUT, BAKED, RAND, 64, HELP, HELP>),
+                           grid_for(W, 64), dim3(128), 0, c.st, c.S.q, c.S.qd, c.V.episode, c.V.steps, c.a, W, c.dt,
+                           c.substeps, c.pgs, A);
+    else if (block_for(W) == 64)
         hipLaunchKernelGGL((dev::vecenv_step_kernel<N, KIND, DUAL, CONS, ROLLOUT, BAKED, RAND, 64, HELP>),
                            grid_for(W, 64), dim3(HELP ? 128 : 64), 0, c.st, c.S.q, c.S.qd, c.V.episode, c.V.steps, c.a,
                            W, c.dt, c.substeps, c.pgs, A);

@@ -5,7 +5,8 @@
 The headline kernel is the closed-loop CartPole step of bench.py:
 vecenv_step_kernel<N=2, KIND=0, DUAL=false, CONS=true, ROLLOUT=false,
 BAKED=cartpole, RAND=false> (64-thread workgroups where the workgroup size is
-a template argument).  The script pulls the gfx950 code objects out of the
+a template argument; the single-substep instantiation where the library has
+one: bench.py runs one substep per step).  The script pulls the gfx950 code objects out of the
 library, disassembles that kernel with the ROCm LLVM tools and prints, as JSON:
 
   kernarg_size              bytes, from the kernel descriptor
@@ -19,6 +20,10 @@ library, disassembles that kernel with the ROCm LLVM tools and prints, as JSON:
                             waiting for the acknowledgement of earlier ones
   lds_bytes                 group_segment_fixed_size of the kernel descriptor
                             (> 0: the workgroup has a helper wave)
+  path_instructions         helper-wave kernels: per role ("wave0", "helper") the
+                            instructions issued and branches taken along the
+                            common path, entry -> s_endpgm (wave 0: a lane
+                            inside W, no limit row, no lane done); see _walk
 
 With preloading, the compiler puts a 256-byte compatibility prologue in front
 of the body (it loads the preloaded arguments by hand, for firmware that does
@@ -38,7 +43,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEFAULT_LIB = os.path.join(ROOT, "gym-ignition_amd", "libmwstep.so")
-HEADLINE = re.compile(r"^_ZN2mw3dev18vecenv_step_kernelILi2ELi0ELb0ELb1ELb0ELi[1-9]\d*ELb0E(Li64E(Lb[01]E)?)?EEv\w*$")
+HEADLINE = re.compile(r"^_ZN2mw3dev18vecenv_step_kernelILi2ELi0ELb0ELb1ELb0ELi[1-9]\d*ELb0E(Li64E(Lb[01]E(Lb1E)?)?)?EEv\w*$")
 # every closed-loop (ROLLOUT == false) instantiation
 CLOSED_LOOP = re.compile(r"^_ZN2mw3dev18vecenv_step_kernelILi\d+ELi\d+ELb[01]ELb[01]ELb0E\w*$")
 BUNDLE_MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
@@ -117,6 +122,118 @@ def analyse(lib_path, pattern=HEADLINE, every=False):
     return found if every else {}
 
 
+class PathError(Exception):
+    """The walk met code that the branch rules of _walk do not describe."""
+
+
+def _target(body, addr, at, k):
+    imm = int(body[k][1].split()[-1], 0) & 0xFFFF
+    return at[addr[k] + 4 + 4 * (imm - 0x10000 if imm & 0x8000 else imm)]
+
+
+def _walk(body, addr, at, role):
+    """Instructions issued and branches taken along the common path of one
+    role of a helper-wave kernel, entry -> s_endpgm.  role "wave0": the
+    physics wave with a lane inside W, no limit row active and no lane done;
+    "helper": the wave that draws the reset state.  The branch decisions:
+
+      * a uniform branch (scc / vcc) from which only one side leads to the
+        role's work (wave 0: a global store; helper: an LDS write) goes there;
+      * any other uniform branch falls through: the code it could skip depends
+        on an argument and runs (substeps >= 1, reward shaping on) -- unless
+        falling through repeats an instruction of the path, the second trip
+        of a loop, which runs once: then it is taken;
+      * s_cbranch_execz is taken: the lanes it guards are those with a limit
+        row, done lanes or lanes whose episode changed, and there are none --
+        except behind the `w < W` test, recognised as the only signed integer
+        vector compare (v_cmp_gt_i32): those lanes exist, it falls through;
+      * s_cbranch_execnz (a lane loop's back edge) falls through.
+
+    The result is checked against what the path must contain (the barrier;
+    wave 0: stores and no LDS read; helper: an LDS write and no store)."""
+    ops = [op for op, _ in body]
+    work = "global_store" if role == "wave0" else "ds_write"
+
+    def reaches_work(k0):
+        seen, todo = set(), [k0]
+        while todo:
+            k = todo.pop()
+            if k in seen or k >= len(body):
+                continue
+            seen.add(k)
+            if ops[k].startswith(work):
+                return True
+            if ops[k] == "s_endpgm":
+                continue
+            if ops[k] == "s_branch":
+                todo.append(_target(body, addr, at, k))
+                continue
+            if ops[k].startswith("s_cbranch"):
+                todo.append(_target(body, addr, at, k))
+            todo.append(k + 1)
+        return False
+
+    def mask_writer(path, mask):
+        for k in reversed(path):
+            if body[k][1].split(",")[0].strip() == mask and not ops[k].startswith("s_cbranch"):
+                return ops[k]
+        return ""
+
+    path, on_path, taken, k = [], set(), 0, 0
+    while True:
+        if k >= len(body) or len(path) > 4 * len(body):
+            raise PathError(f"{role}: the walk left the kernel or does not end")
+        path.append(k)
+        on_path.add(k)
+        op = ops[k]
+        if op == "s_endpgm":
+            break
+        if op == "s_branch":
+            k, taken = _target(body, addr, at, k), taken + 1
+            continue
+        if not op.startswith("s_cbranch"):
+            k += 1
+            continue
+        tgt = _target(body, addr, at, k)
+        if op in ("s_cbranch_execz", "s_cbranch_execnz"):
+            take = False
+            if op == "s_cbranch_execz":
+                # the instruction that set exec: s_and_saveexec_b64 d, m / s_and_b64 exec, exec, m
+                setter = next((j for j in reversed(path[:-1]) if ops[j].startswith("s_and_saveexec") or
+                               (ops[j] == "s_and_b64" and body[j][1].startswith("exec, exec,"))), None)
+                if setter is None:
+                    raise PathError(f"{role}: no exec mask in front of {op}")
+                mask = body[setter][1].split(",")[-1].strip()
+                take = not mask_writer(path[:path.index(setter)], mask).startswith("v_cmp_gt_i32")
+        else:
+            sides = [reaches_work(tgt), reaches_work(k + 1)]
+            if sides[0] != sides[1]:
+                take = sides[0]
+            else:
+                take = (k + 1) in on_path
+        if take:
+            k, taken = tgt, taken + 1
+        else:
+            k += 1
+    pops = [ops[j] for j in path]
+    ok = "s_barrier" in pops
+    if role == "wave0":
+        ok = ok and any(p.startswith("global_store") for p in pops) and not any(p.startswith("ds_read") for p in pops)
+    else:
+        ok = ok and any(p.startswith("ds_write") for p in pops) and not any(p.startswith("global_store") for p in pops)
+    if not ok:
+        raise PathError(f"{role}: the walked path is not the role's common path")
+    return {"instructions": len(path), "taken_branches": taken,
+            "stores": sum(p.startswith("global_store") for p in pops)}
+
+
+def path_instructions(lib_path, pattern=HEADLINE):
+    """{"wave0": {...}, "helper": {...}} of the kernel that `pattern` selects:
+    see _walk.  None without the LLVM tools; {} if there is no such kernel."""
+    res = analyse(lib_path, pattern)
+    return res["path_instructions"] if res else res
+
+
 def _counts(lib_path, elf, path, objdump, name, func_at, kd_at):
     kd = elf_bytes_at(elf, kd_at, 64)   # amd_kernel_code descriptor, 64 bytes
     lds_bytes, = struct.unpack_from("<I", kd, 0)   # group_segment_fixed_size
@@ -156,7 +273,12 @@ def _counts(lib_path, elf, path, objdump, name, func_at, kd_at):
         if k not in after_store:
             after_store.add(k)
             todo.extend(succ[k])
+    try:
+        paths = {role: _walk(body, addr, at, role) for role in ("wave0", "helper")} if lds_bytes else None
+    except PathError as e:
+        paths = {"error": str(e)}
     return {
+        "path_instructions": paths,
         "library": os.path.basename(lib_path),
         "kernel": name,
         "kernarg_size": kernarg_size,
