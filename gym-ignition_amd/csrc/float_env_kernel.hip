@@ -11,7 +11,11 @@
 // the post launch's PUSH instance reports the push the run applied and writes
 // the next step's into the run kernel's wrench array, its RAND instance draws
 // the friction of every episode it starts into the simulator's per-world
-// array (T.rand.mu).
+// array (T.rand.mu).  The locomotion task (mw_floatenv_locomotion) is the LOCO
+// instance of both env kernels: the action launch keeps the raw action and the
+// action-rate sum and writes the scaled command, the post launch appends the
+// body-frame block of the observation, draws the velocity commands and adds
+// the tracking / smoothness / air-time terms to the reward.
 //
 // Both kernels are transposes between the row-major [W, k] tensors of the
 // agent and the [k][W] SoA arrays of the simulator.  A block of 256 threads
@@ -43,13 +47,32 @@ constexpr int kEnvWaves = kEnvThreads / 64;
 // NaN target: a world whose action holds a non-finite value is therefore
 // flagged diverged here (sticky flag + count, as the run kernels flag a
 // non-finite state), so that the post kernel ends and resets it.
+// LOCO (the locomotion task): the raw action of every world is kept row-major
+// in A.prev [W][n] -- the same contiguous span as the input, read and written
+// by the thread that stages the word -- after sum_d (a_t - a_{t-1})^2 went to
+// A.rate [W] through a second tile of the differences (a reset zeroes the kept
+// row, so a_{t-1} = 0 on an episode's first step).  With A.scale > 0 the value
+// stored is home_q[d] + scale a_d (position mode, one fused multiply-add) or
+// scale a_d (torque mode); sum a^2 and the non-finite test stay on the raw action.
+template <bool LOCO>
+struct ActLocoArgs {};
+template <>
+struct ActLocoArgs<true> {
+    float scale;
+    int32_t position;
+    float* prev;
+    float* rate;
+    float home_q[kMaxBodies];
+};
+
+template <bool LOCO>
 __global__ void __launch_bounds__(kEnvThreads) float_env_action_kernel(const float* __restrict__ actions,
                                                                        float* __restrict__ out,
                                                                        float* __restrict__ asq,
                                                                        uint8_t* __restrict__ div,
                                                                        unsigned long long* __restrict__ ndiv, int n,
-                                                                       int W) {
-    extern __shared__ float tile[];  // [kEnvTile][n | 1]
+                                                                       int W, ActLocoArgs<LOCO> A) {
+    extern __shared__ float tile[];  // [kEnvTile][n | 1]; LOCO: then [kEnvTile][n | 1] of a_t - a_{t-1}
     const int pitch = n | 1;
     const int w0 = blockIdx.x * kEnvTile;
     const int rows = min(kEnvTile, W - w0);
@@ -57,13 +80,28 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_action_kernel(const flo
     // the tile's rows are one contiguous span of rows * n words
     for (int i = threadIdx.x; i < rows * n; i += kEnvThreads) {
         const int r = i / n, d = i - r * n;
-        tile[r * pitch + d] = src[i];
+        const float a = src[i];
+        tile[r * pitch + d] = a;
+        if constexpr (LOCO) {
+            float* prev = A.prev + static_cast<size_t>(w0) * n;
+            tile[(kEnvTile + r) * pitch + d] = a - prev[i];
+            prev[i] = a;
+        }
     }
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane >= rows) return;
     const float* row = tile + lane * pitch;
-    for (int d = wave; d < n; d += kEnvWaves) out[static_cast<size_t>(d) * W + w0 + lane] = row[d];
+    for (int d = wave; d < n; d += kEnvWaves) {
+        float v = row[d];
+        if constexpr (LOCO) {
+            if (A.scale > 0.f) v = A.position ? fmaf(A.scale, v, A.home_q[d]) : A.scale * v;
+        }
+        out[static_cast<size_t>(d) * W + w0 + lane] = v;
+    }
+    if constexpr (LOCO) {
+        if (wave == 1) A.rate[w0 + lane] = ft_sum_sq(tile + (kEnvTile + lane) * pitch, n, 1);
+    }
     if (wave == 0) {
         asq[w0 + lane] = ft_sum_sq(row, n, 1);
         bool bad = false;
@@ -93,7 +131,18 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_action_kernel(const flo
 // (seed, global world, episode, steps taken), all known here once the counters
 // are updated: the episode's phase from its episode block, push k's (fx, fy,
 // tz) from block kFtPushBlock | k (float_task.hpp).
-template <bool RAND, bool PUSH>
+// LOCO (T.loco.on): the row grows by 12 + n words behind the NB = 13 + 2 n +
+// n_links of the plain env -- projected gravity, body-frame linear and angular
+// velocity (wave 0, from the base words it holds), the command in force for
+// the next step (wave 3) and the raw action the step applied (every thread,
+// the kept rows of the action launch as one contiguous span).  Wave 3 draws
+// the command the step ran under (steps taken t, for the reward) and the one
+// of t + 1 (for obs and terminal_obs) during the gather, before the counters
+// move, and the new episode's command 0 with the resets; the waves that sum a
+// link's contact force also step its air-time counter and leave the touchdown
+// payment in LDS for wave 0's reward.  A reset zeroes the kept action row and
+// the air counters.
+template <bool RAND, bool PUSH, bool LOCO>
 __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const ChainF* __restrict__ P, FloatTaskF T,
                                                                      SimDev S, FreeDev D, VecDev V,
                                                                      const float* __restrict__ asq,
@@ -106,7 +155,10 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
     __shared__ uint8_t s_done[kEnvTile];
     __shared__ uint32_t s_episode[kEnvTile];
     __shared__ uint32_t s_steps[kEnvTile];  // PUSH: steps taken in the episode the next step belongs to
+    __shared__ float s_cmd[LOCO ? 3 * kEnvTile : 1];                 // the command the step ran under
+    __shared__ float s_pay[LOCO ? kMaxContactLinks * kEnvTile : 1];  // touchdown payment per link
     const int NO = T.n_obs, pitch = NO | 1;
+    const int NB = 13 + 2 * n + T.n_links;  // LOCO: the appended block starts here
     const int w0 = blockIdx.x * kEnvTile;
     const int rows = min(kEnvTile, W - w0);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -115,6 +167,13 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
     float* row = tile + lane * pitch;
     const size_t Ws = static_cast<size_t>(W);
     if (!reset_all) {
+        if constexpr (LOCO) {
+            const float* __restrict__ kept = T.loco.prev_action + static_cast<size_t>(w0) * n;
+            for (int i = threadIdx.x; i < rows * n; i += kEnvThreads) {
+                const int r = i / n, d = i - r * n;
+                tile[r * pitch + NB + 12 + d] = kept[i];
+            }
+        }
         // gather: lane = world, the waves split the words
         if (live) {
             if (wave == 0) {
@@ -126,6 +185,16 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
                 for (int k = 0; k < 7; ++k) row[k] = b[k];
 #pragma unroll
                 for (int k = 0; k < 3; ++k) { row[7 + k] = lin[k]; row[10 + k] = ang[k]; }
+                if constexpr (LOCO) {
+                    float g[3];
+                    ft_projected_gravity(b[3], b[4], b[5], b[6], g);
+#pragma unroll
+                    for (int k = 0; k < 3; ++k) {
+                        row[NB + k] = g[k];
+                        row[NB + 3 + k] = b[10 + k];
+                        row[NB + 6 + k] = b[7 + k];
+                    }
+                }
             }
             for (int k = wave; k < 2 * n; k += kEnvWaves)
                 row[13 + k] = (k < n) ? S.q[k * Ws + w] : S.qd[(k - n) * Ws + w];
@@ -135,6 +204,27 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
                 for (uint32_t m = D.cmask[w] & T.link_slots[j]; m; m &= m - 1u)
                     f += D.cdata[(static_cast<size_t>(__builtin_ctz(m)) * 7 + 5) * Ws + w];
                 row[13 + 2 * n + j] = f;
+                if constexpr (LOCO) {
+                    uint32_t air = T.loco.air_steps[j * Ws + w];
+                    s_pay[j * kEnvTile + lane] = ft_air_step(T.loco, f, air);
+                    T.loco.air_steps[j * Ws + w] = air;
+                }
+            }
+            if (LOCO && wave == 3) {
+                const uint32_t g = T.world_offset + static_cast<uint32_t>(w), episode = V.episode[w], t = V.steps[w];
+                const uint32_t k0 = ft_cmd_index(t, T.loco.cmd_interval), k1 = ft_cmd_index(t + 1u, T.loco.cmd_interval);
+                uint32_t r[4];
+                float c[3];
+                philox(T.seed_lo, T.seed_hi, g, episode, r, ft_cmd_block(k0));
+                ft_command(T.loco, r, c);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) s_cmd[k * kEnvTile + lane] = c[k];
+                if (k1 != k0) {
+                    philox(T.seed_lo, T.seed_hi, g, episode, r, ft_cmd_block(k1));
+                    ft_command(T.loco, r, c);
+                }
+#pragma unroll
+                for (int k = 0; k < 3; ++k) row[NB + 9 + k] = c[k];
             }
         }
         __syncthreads();
@@ -145,7 +235,16 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
                 const bool term = ft_terminated(row[2], ft_tilt(row[4], row[5]), S.div[w] != 0, T.z_min, T.cos_tilt_max);
                 uint32_t steps = V.steps[w] + 1u;
                 done = term || (T.max_steps > 0 && steps >= static_cast<uint32_t>(T.max_steps));
-                reward[w] = ft_reward(T, term, row[7], asq[w], ft_sum_sq_diff(row + 13, 1, T.home_q, n));
+                float rew = ft_reward(T, term, row[7], asq[w], ft_sum_sq_diff(row + 13, 1, T.home_q, n));
+                if constexpr (LOCO) {
+                    const float cmd[3] = {s_cmd[lane], s_cmd[kEnvTile + lane], s_cmd[2 * kEnvTile + lane]};
+                    const float v[3] = {row[NB + 3], row[NB + 4], row[NB + 5]};
+                    const float om[3] = {row[NB + 6], row[NB + 7], row[NB + 8]};
+                    float pay = 0.f;
+                    for (int j = 0; j < T.n_links; ++j) pay += s_pay[j * kEnvTile + lane];
+                    rew = ft_loco_reward(T.loco, rew, cmd, v, om, T.loco.action_rate[w], pay);
+                }
+                reward[w] = rew;
                 done_out[w] = done ? 1 : 0;
                 episode = V.episode[w];
                 if (done) {
@@ -233,6 +332,16 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
             }
             D.rflag[w] = 1u | 2u;
             S.div[w] = 0;  // a reset re-arms the divergence flag (mw_reset_* do)
+            if constexpr (LOCO) {
+                float g[3];
+                ft_projected_gravity(T.home_base[3], T.home_base[4], T.home_base[5], T.home_base[6], g);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    row[NB + k] = g[k];
+                    row[NB + 3 + k] = 0.f;
+                    row[NB + 6 + k] = 0.f;
+                }
+            }
         }
         if (RAND && wave == 1) {
             uint32_t r[4];
@@ -241,7 +350,29 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
             T.rand.mu[w] = mu;
             if (T.rand.friction_out) T.rand.friction_out[w] = mu;
         }
-        for (int j = wave; j < T.n_links; j += kEnvWaves) row[13 + 2 * n + j] = 0.f;
+        for (int j = wave; j < T.n_links; j += kEnvWaves) {
+            row[13 + 2 * n + j] = 0.f;
+            if constexpr (LOCO) T.loco.air_steps[j * Ws + w] = 0u;
+        }
+        if constexpr (LOCO) {
+            for (int d = wave; d < n; d += kEnvWaves) {
+                row[NB + 12 + d] = 0.f;
+                T.loco.prev_action[static_cast<size_t>(w) * n + d] = 0.f;
+            }
+            if (wave == 3) {
+                uint32_t r[4];
+                float c[3];
+                philox(T.seed_lo, T.seed_hi, T.world_offset + static_cast<uint32_t>(w), episode, r, ft_cmd_block(0u));
+                ft_command(T.loco, r, c);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) row[NB + 9 + k] = c[k];
+            }
+        }
+    }
+    if (LOCO && wave == 3 && live && T.loco.command_out) {
+        // the words this thread wrote itself: the gather's, or the reset's over them
+#pragma unroll
+        for (int k = 0; k < 3; ++k) T.loco.command_out[static_cast<size_t>(w) * 3 + k] = row[NB + 9 + k];
     }
     __syncthreads();
     for (int r = wave; r < rows; r += kEnvWaves)
@@ -253,8 +384,24 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
 hipError_t launch_float_env_action(const float* actions, float* out, float* asq, uint8_t* div,
                                    unsigned long long* ndiv, int n, int W, hipStream_t st) {
     const size_t lds = static_cast<size_t>(dev::kEnvTile) * (n | 1) * sizeof(float);
-    hipLaunchKernelGGL(dev::float_env_action_kernel, dim3((W + dev::kEnvTile - 1) / dev::kEnvTile),
-                       dim3(dev::kEnvThreads), lds, st, actions, out, asq, div, ndiv, n, W);
+    hipLaunchKernelGGL(dev::float_env_action_kernel<false>, dim3((W + dev::kEnvTile - 1) / dev::kEnvTile),
+                       dim3(dev::kEnvThreads), lds, st, actions, out, asq, div, ndiv, n, W,
+                       dev::ActLocoArgs<false>{});
+    return hipGetLastError();
+}
+
+hipError_t launch_float_env_action_loco(const FloatTaskF& T, const float* actions, float* out, float* asq,
+                                        uint8_t* div, unsigned long long* ndiv, int n, int W, hipStream_t st) {
+    dev::ActLocoArgs<true> A;
+    A.scale = T.loco.action_scale;
+    A.position = T.action_mode;
+    A.prev = T.loco.prev_action;
+    A.rate = T.loco.action_rate;
+    for (int d = 0; d < kMaxBodies; ++d) A.home_q[d] = T.home_q[d];
+    // two tiles: at most 2 x 64 x 49 words = 25 KB
+    const size_t lds = 2 * static_cast<size_t>(dev::kEnvTile) * (n | 1) * sizeof(float);
+    hipLaunchKernelGGL(dev::float_env_action_kernel<true>, dim3((W + dev::kEnvTile - 1) / dev::kEnvTile),
+                       dim3(dev::kEnvThreads), lds, st, actions, out, asq, div, ndiv, n, W, A);
     return hipGetLastError();
 }
 
@@ -263,14 +410,24 @@ hipError_t launch_float_env_post(const ChainF* P, const FloatTaskF& T, const Sim
                                  float* term_obs, int n, int W, int reset_all, hipStream_t st) {
     const size_t lds = static_cast<size_t>(dev::kEnvTile) * (T.n_obs | 1) * sizeof(float);
     const dim3 grid((W + dev::kEnvTile - 1) / dev::kEnvTile), block(dev::kEnvThreads);
-    const bool rand = T.rand.friction_hi > 0.f, push = T.rand.push_interval > 0u;
-#define MW_POST(R_, P_)                                                                                          \
-    hipLaunchKernelGGL((dev::float_env_post_kernel<R_, P_>), grid, block, lds, st, P, T, S, D, V, asq, obs, reward, \
-                       done, term_obs, n, W, reset_all)
-    if (rand && push) MW_POST(true, true);
-    else if (rand) MW_POST(true, false);
-    else if (push) MW_POST(false, true);
-    else MW_POST(false, false);
+    // The locomotion rows are 25 + 3 n + n_links words: at most (48 dofs, 8
+    // links) 64 x 177 words = 45 KB, with the kernel's 3.3 KB of static LDS
+    // still inside the 64 KB a block gets without asking for more.
+    const bool rand = T.rand.friction_hi > 0.f, push = T.rand.push_interval > 0u, loco = T.loco.on != 0u;
+#define MW_POST(R_, P_, L_)                                                                                     \
+    hipLaunchKernelGGL((dev::float_env_post_kernel<R_, P_, L_>), grid, block, lds, st, P, T, S, D, V, asq, obs, \
+                       reward, done, term_obs, n, W, reset_all)
+#define MW_POST_RP(L_)                       \
+    if (rand && push) MW_POST(true, true, L_);   \
+    else if (rand) MW_POST(true, false, L_);     \
+    else if (push) MW_POST(false, true, L_);     \
+    else MW_POST(false, false, L_)
+    if (loco) {
+        MW_POST_RP(true);
+    } else {
+        MW_POST_RP(false);
+    }
+#undef MW_POST_RP
 #undef MW_POST
     return hipGetLastError();
 }

@@ -5,7 +5,10 @@
 // tests/host_float_task/harness.cpp builds the same code with g++ against
 // numpy fp64.  The Philox reset sampling stays in rng.hpp (device only); the
 // integer arithmetic of the push schedule (mw_floatenv_randomize) is here too,
-// built by tests/host_float_rand/harness.cpp.
+// built by tests/host_float_rand/harness.cpp, and so is the arithmetic of the
+// locomotion task (mw_floatenv_locomotion: commands, projected gravity, the
+// air-time counter, the extra reward terms), built by
+// tests/host_float_loco/harness.cpp.
 #pragma once
 
 #ifdef MW_HOST_TEST
@@ -46,6 +49,27 @@ struct FloatRandF {
 // blocks 0 .. (n + 3) / 4 - 1 of the same (world, episode) counter.
 constexpr uint32_t kFtEpisodeBlock = 0x40000000u;  // r[0]: push phase, r[1]: friction
 constexpr uint32_t kFtPushBlock = 0x80000000u;     // | k: push k of the episode (fx, fy, tz)
+constexpr uint32_t kFtCmdBlock = 0xC0000000u;      // | k: command k of the episode (v_x, v_y, yaw rate, zero test)
+
+// Locomotion task of the floating-base env (mw_floatenv_locomotion), off when
+// `on` is zero: a per-world velocity command, the body-frame block of the
+// observation, scaled actions and the tracking / smoothness / air-time terms
+// of the reward.
+struct FloatLocoF {
+    uint32_t on;
+    uint32_t cmd_interval;       // steps between command draws, 0 = one per episode
+    float cmd_lo[3], cmd_hi[3];  // v_x, v_y (m/s), yaw rate (rad/s), body frame
+    float cmd_zero_prob;         // a draw is the zero command with this probability
+    float cmd_min;               // v_x^2 + v_y^2 <= cmd_min^2: no air-time term
+    float action_scale;          // 0 = raw actions
+    float w_track_lin, w_track_yaw, track_sigma, w_lin_z, w_ang_xy, w_action_rate;
+    float w_air_time, air_time_target, contact_force_min;
+    float env_dt;                // steps_per_run * step_size (s)
+    float* prev_action;          // [W][n] the raw action of the last step, zeros after a reset
+    uint32_t* air_steps;         // [n_links][W] steps without contact since the last touchdown
+    float* action_rate;          // [W] sum_d (a_t - a_{t-1})^2 of the last step
+    float* command_out;          // [W, 3] the command in force for the next step (caller's, may be null)
+};
 
 // Task description of the floating-base env (kernel argument, by value).
 struct FloatTaskF {
@@ -62,6 +86,7 @@ struct FloatTaskF {
     uint32_t link_slots[kMaxContactLinks];  // contact slots (FreeDev::cmask bits) of every contact link
     float home_q[kMaxBodies];
     FloatRandF rand;
+    FloatLocoF loco;
 };
 
 namespace dev {
@@ -129,6 +154,65 @@ __device__ __forceinline__ float ft_sum_sq_diff(const float* x, size_t stride, c
 __device__ __forceinline__ float ft_reward(const FloatTaskF& T, bool terminated, float vx, float sum_a2,
                                            float sum_pose2) {
     return (terminated ? 0.f : T.alive_bonus) + T.w_forward * vx - T.w_action * sum_a2 - T.w_pose * sum_pose2;
+}
+
+// ---- locomotion task (FloatLocoF) ----
+
+// rng.hpp's unif(), restated here so that the host harnesses build it:
+// lo + (hi - lo) (x >> 8) 2^-24.
+__device__ __forceinline__ float ft_unif(uint32_t x, float lo, float hi) {
+    return lo + (hi - lo) * (static_cast<float>(x >> 8) * (1.f / 16777216.f));
+}
+
+// The command schedule is a pure function of (seed, global world, episode, t),
+// t the steps already taken in the episode: command k = t / cmd_interval (0
+// with one command per episode) comes from the Philox block kFtCmdBlock | k
+// (k < 2^30).
+__device__ __forceinline__ uint32_t ft_cmd_index(uint32_t t, uint32_t interval) { return interval ? t / interval : 0u; }
+__device__ __forceinline__ uint32_t ft_cmd_block(uint32_t k) { return kFtCmdBlock | (k & 0x3FFFFFFFu); }
+// r[0..2] into the three ranges; the zero command where U(0, 1) of r[3] (an
+// exact float32: (r[3] >> 8) 2^-24) is below cmd_zero_prob.
+__device__ __forceinline__ bool ft_cmd_is_zero(uint32_t r3, float zero_prob) { return ft_unif(r3, 0.f, 1.f) < zero_prob; }
+__device__ __forceinline__ void ft_command(const FloatLocoF& L, const uint32_t (&r)[4], float (&cmd)[3]) {
+    const bool zero = ft_cmd_is_zero(r[3], L.cmd_zero_prob);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) cmd[k] = zero ? 0.f : ft_unif(r[k], L.cmd_lo[k], L.cmd_hi[k]);
+}
+
+// World -z in the body frame: minus the last row of the base's rotation.
+__device__ __forceinline__ void ft_projected_gravity(float qw, float qx, float qy, float qz, float (&g)[3]) {
+    g[0] = -(2.f * (qx * qz - qw * qy));
+    g[1] = -(2.f * (qy * qz + qw * qx));
+    g[2] = -(1.f - 2.f * (qx * qx + qy * qy));
+}
+
+// One step of a link's air-time bookkeeping: without contact the counter
+// grows; the first step with contact after a flight is the touchdown, which
+// pays (air_steps env_dt - air_time_target) and zeroes the counter.
+__device__ __forceinline__ float ft_air_step(const FloatLocoF& L, float fz, uint32_t& air_steps) {
+    if (!(fz > L.contact_force_min)) {
+        air_steps += 1u;
+        return 0.f;
+    }
+    const uint32_t flown = air_steps;
+    air_steps = 0u;
+    return flown ? static_cast<float>(flown) * L.env_dt - L.air_time_target : 0.f;
+}
+
+// The locomotion terms on top of ft_reward's four: v, w the body-frame linear
+// and angular velocity of the base, cmd the command the step ran under, rate
+// sum (a_t - a_{t-1})^2, air_pay the links' touchdown payments summed.
+__device__ __forceinline__ float ft_loco_reward(const FloatLocoF& L, float base_reward, const float (&cmd)[3],
+                                                const float (&v)[3], const float (&w)[3], float rate, float air_pay) {
+    const float ex = cmd[0] - v[0], ey = cmd[1] - v[1], ew = cmd[2] - w[2];
+    float r = base_reward;
+    r += L.w_track_lin * expf(-(ex * ex + ey * ey) / L.track_sigma);
+    r += L.w_track_yaw * expf(-(ew * ew) / L.track_sigma);
+    r -= L.w_lin_z * (v[2] * v[2]);
+    r -= L.w_ang_xy * (w[0] * w[0] + w[1] * w[1]);
+    r -= L.w_action_rate * rate;
+    if (cmd[0] * cmd[0] + cmd[1] * cmd[1] > L.cmd_min * L.cmd_min) r += L.w_air_time * air_pay;
+    return r;
 }
 
 }  // namespace dev

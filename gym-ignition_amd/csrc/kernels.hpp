@@ -172,6 +172,17 @@ hipError_t launch_vecenv_pid_group(const ChainF* P, int n, bool cons, bool dual,
 // reset_all: every world starts episode 0, only obs is written.
 hipError_t launch_float_env_action(const float* actions, float* out, float* asq, uint8_t* div,
                                    unsigned long long* ndiv, int n, int W, hipStream_t st);
+// With the locomotion task on (mw_floatenv_locomotion, T.loco.on) both launches
+// run their LOCO instances: this action launch, which takes the task, keeps
+// the raw action (T.loco.prev_action) and sum (a_t - a_{t-1})^2
+// (T.loco.action_rate) and scales what it stores; the post launch appends
+// 12 + n words to every row.  Declared weak: the sanitizer harness links the
+// host layer against a stand-in of the launchers (tests/sanitize) that has no
+// locomotion launcher, and mw_floatenv_locomotion refuses to turn the task on
+// where the symbol is absent.
+hipError_t launch_float_env_action_loco(const struct FloatTaskF& T, const float* actions, float* out, float* asq,
+                                        uint8_t* div, unsigned long long* ndiv, int n, int W, hipStream_t st)
+    __attribute__((weak));
 // With randomisation on (mw_floatenv_randomize, T.rand) the post launch also
 // copies the base wrench the run applied (node 0 of D.wrench) into
 // T.rand.push_out and writes the next step's in its place (zeros where no push

@@ -3,6 +3,7 @@
 // state (vecenv_kernel.hip, group_kernel.hip, float_env_kernel.hip).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -30,7 +31,12 @@ struct mw_vecenv {
     bool floatenv = false;
     mw::FloatTaskF ftask{};
     mw::dev_ptr<float[]> d_asq;
-    bool was_reset = false;  // mw_vecenv_reset ran: mw_floatenv_randomize comes too late
+    bool was_reset = false;  // mw_vecenv_reset ran: mw_floatenv_randomize / _locomotion come too late
+    // locomotion task (mw_floatenv_locomotion): the kept action rows [W][n], the
+    // air-time counters [n_links][W] and the action-rate sums [W]
+    mw::dev_ptr<float[]> d_prev_action;
+    mw::dev_ptr<uint32_t[]> d_air_steps;
+    mw::dev_ptr<float[]> d_action_rate;
 
     // the env's work (on its simulator's stream) drains before the members release their buffers
     ~mw_vecenv() { if (sim && sim->stream) (void)hipStreamSynchronize(sim->stream); }
@@ -272,6 +278,76 @@ int mw_floatenv_randomize(mw_vecenv* e, const mw_float_rand_config* cfg, float* 
     return MW_OK;
 }
 
+// The locomotion task: a per-world velocity command drawn by the post launch,
+// the body-frame block of the observation, scaled actions and the tracking /
+// smoothness / air-time reward terms, all inside the step's three launches
+// (the LOCO instances of float_env_kernel.hip).
+int mw_floatenv_locomotion(mw_vecenv* e, const mw_float_loco_config* cfg, float* command_out) {
+    if (!e || !cfg) return fail(MW_EINVAL, "null argument");
+    if (!e->floatenv) return fail(MW_ESTATE, "mw_floatenv_locomotion needs an env made by mw_floatenv_create");
+    if (e->was_reset) return fail(MW_ESTATE, "mw_floatenv_locomotion must be called before the first mw_vecenv_reset");
+    if (!mw::launch_float_env_action_loco) return fail(MW_ESTATE, "this build has no locomotion kernels");
+    const float fields[] = {cfg->cmd_lo[0], cfg->cmd_lo[1], cfg->cmd_lo[2], cfg->cmd_hi[0], cfg->cmd_hi[1],
+                            cfg->cmd_hi[2], cfg->cmd_zero_prob, cfg->cmd_min, cfg->action_scale, cfg->w_track_lin,
+                            cfg->w_track_yaw, cfg->track_sigma, cfg->w_lin_z, cfg->w_ang_xy, cfg->w_action_rate,
+                            cfg->w_air_time, cfg->air_time_target, cfg->contact_force_min};
+    for (float f : fields)
+        if (!std::isfinite(f)) return fail(MW_EINVAL, "every field of mw_float_loco_config must be finite");
+    for (int k = 0; k < 3; ++k)
+        if (cfg->cmd_hi[k] < cfg->cmd_lo[k]) return fail(MW_EINVAL, "the command ranges need cmd_lo <= cmd_hi");
+    if (cfg->cmd_interval < 0) return fail(MW_EINVAL, "cmd_interval must be >= 0");
+    if (cfg->cmd_zero_prob < 0.f || cfg->cmd_zero_prob > 1.f) return fail(MW_EINVAL, "cmd_zero_prob must be in [0, 1]");
+    if (!(cfg->track_sigma > 0.f)) return fail(MW_EINVAL, "track_sigma must be > 0");
+    if (cfg->action_scale < 0.f) return fail(MW_EINVAL, "action_scale must be >= 0");
+    if (cfg->w_air_time != 0.f && e->ftask.n_links == 0)
+        return fail(MW_EINVAL, "the air-time term (w_air_time != 0) needs contact links");
+    mw_sim* s = e->sim;
+    const size_t W = static_cast<size_t>(s->W), n = static_cast<size_t>(s->n);
+    const size_t links = static_cast<size_t>(e->ftask.n_links > 0 ? e->ftask.n_links : 1);
+    MW_HIP(hipSetDevice(s->cfg.device));
+    // the allocations first: a failed call leaves the env as it was
+    mw::dev_ptr<float[]> prev, rate;
+    mw::dev_ptr<uint32_t[]> air;
+    MW_HIP(mw::dev_alloc(prev, W * n * sizeof(float)));
+    MW_HIP(mw::dev_alloc(air, links * W * sizeof(uint32_t)));
+    MW_HIP(mw::dev_alloc(rate, W * sizeof(float)));
+    MW_HIP(hipMemsetAsync(prev.get(), 0, W * n * sizeof(float), s->stream));
+    MW_HIP(hipMemsetAsync(air.get(), 0, links * W * sizeof(uint32_t), s->stream));
+    MW_HIP(hipMemsetAsync(rate.get(), 0, W * sizeof(float), s->stream));
+    e->d_prev_action = std::move(prev);
+    e->d_air_steps = std::move(air);
+    e->d_action_rate = std::move(rate);
+    mw::FloatTaskF& T = e->ftask;
+    mw::FloatLocoF& L = T.loco;
+    L = mw::FloatLocoF{};
+    L.on = 1u;
+    L.cmd_interval = static_cast<uint32_t>(cfg->cmd_interval);
+    for (int k = 0; k < 3; ++k) {
+        L.cmd_lo[k] = cfg->cmd_lo[k];
+        L.cmd_hi[k] = cfg->cmd_hi[k];
+    }
+    L.cmd_zero_prob = cfg->cmd_zero_prob;
+    L.cmd_min = cfg->cmd_min;
+    L.action_scale = cfg->action_scale;
+    L.w_track_lin = cfg->w_track_lin;
+    L.w_track_yaw = cfg->w_track_yaw;
+    L.track_sigma = cfg->track_sigma;
+    L.w_lin_z = cfg->w_lin_z;
+    L.w_ang_xy = cfg->w_ang_xy;
+    L.w_action_rate = cfg->w_action_rate;
+    L.w_air_time = cfg->w_air_time;
+    L.air_time_target = cfg->air_time_target;
+    L.contact_force_min = cfg->contact_force_min;
+    L.env_dt = static_cast<float>(s->cfg.steps_per_run * s->cfg.step_size);
+    L.prev_action = e->d_prev_action.get();
+    L.air_steps = e->d_air_steps.get();
+    L.action_rate = e->d_action_rate.get();
+    L.command_out = command_out;
+    T.n_obs = 25 + 3 * s->n + T.n_links;
+    e->task.n_obs = T.n_obs;  // mw_vecenv_obs_dim
+    return MW_OK;
+}
+
 static int floatenv_reset(mw_vecenv* e, float* obs) {
     mw_sim* s = e->sim;
     e->was_reset = true;
@@ -285,8 +361,12 @@ static int floatenv_reset(mw_vecenv* e, float* obs) {
 static int floatenv_step(mw_vecenv* e, const void* a, float* o, float* r, uint8_t* d, float* to) {
     mw_sim* s = e->sim;
     const bool pos = e->ftask.action_mode == MW_FLOAT_ACTION_POSITION;
-    MW_HIP(mw::launch_float_env_action(static_cast<const float*>(a), pos ? s->dev.ptgt : s->dev.cmd, e->d_asq.get(),
-                                       s->dev.div, s->dev.ndiv, s->n, s->W, s->stream));
+    if (e->ftask.loco.on)
+        MW_HIP(mw::launch_float_env_action_loco(e->ftask, static_cast<const float*>(a), pos ? s->dev.ptgt : s->dev.cmd,
+                                                e->d_asq.get(), s->dev.div, s->dev.ndiv, s->n, s->W, s->stream));
+    else
+        MW_HIP(mw::launch_float_env_action(static_cast<const float*>(a), pos ? s->dev.ptgt : s->dev.cmd, e->d_asq.get(),
+                                           s->dev.div, s->dev.ndiv, s->n, s->W, s->stream));
     if (pos) s->ptgt_stale = true;  // the host mirror of the targets re-reads the device copy
     if (int rc = run_impl(s, 0, false)) return rc;
     MW_HIP(mw::launch_float_env_post(s->d_params.get(), e->ftask, s->dev, s->fdev, e->dev, e->d_asq.get(), o, r, d, to,

@@ -23,6 +23,15 @@ With pushes on it also owns the simulator's wrench buffer
 (``apply_world_wrench`` raises), with friction randomisation on the per-world
 ground friction (``set_ground_friction`` / ``set_ground_plane`` raise,
 ``ground_friction()`` reads the device copy).
+
+``task="locomotion"`` (``mw_floatenv_locomotion``) turns the env into a
+velocity-command task, still three launches per step: every world follows a
+command (v_x, v_y, yaw rate in the body frame) drawn on the device, the
+observation grows by projected gravity (3), body-frame linear (3) and angular
+(3) velocity, the command (3) and the last raw action (n) -- ``25 + 3 n +
+n_contact_links`` words, ``env.obs_slices`` names them --, actions may be
+scaled around the home posture, and the reward gains command-tracking,
+vertical / roll-pitch velocity, action-rate and feet-air-time terms.
 """
 
 from __future__ import annotations
@@ -40,6 +49,7 @@ from .models import get_model_file
 from .sim import Simulator
 
 ACTION_MODES = {"torque": N.FLOAT_ACTION_TORQUE, "position": N.FLOAT_ACTION_POSITION}
+TASKS = ("forward", "locomotion")
 MAX_CONTACT_LINKS = 8
 
 
@@ -73,7 +83,14 @@ class FloatVecEnv:
                  seed: int = 42, world_offset: int = 0, step_size: float = 1e-3, steps_per_run: int = 1,
                  device: int = 0, pgs_iters: int = 20, ground_mu: float = 1.0,
                  push_interval: int = 0, push_steps: int = 1, push_force: float = 0.0, push_torque: float = 0.0,
-                 friction_range: Optional[Sequence[float]] = None):
+                 friction_range: Optional[Sequence[float]] = None,
+                 task: str = "forward",
+                 command_ranges: Sequence[Sequence[float]] = ((0.0, 0.0), (0.0, 0.0), (0.0, 0.0)),
+                 cmd_interval: int = 0, cmd_zero_prob: float = 0.0, cmd_min: float = 0.0,
+                 action_scale: float = 0.0, w_track_lin: float = 1.0, w_track_yaw: float = 0.5,
+                 track_sigma: float = 0.25, w_lin_z: float = 0.0, w_ang_xy: float = 0.0,
+                 w_action_rate: float = 0.0, w_air_time: float = 0.0, air_time_target: float = 0.0,
+                 contact_force_min: float = 1.0):
         """``model``: a shipped model's name or a URDF / SDF file.  ``home_q``
         (one value per dof) and ``home_base`` (x y z qw qx qy qz) are the reset
         state; ``pid_gains`` per dof ``(p, i, d)`` or the eight values of
@@ -91,15 +108,40 @@ class FloatVecEnv:
         ``(lo, hi)`` draws every world's ground friction anew at each reset.
         ``env.push`` ``[n_worlds, 6]`` holds the wrench the last step applied and
         ``env.friction`` ``[n_worlds]`` the current coefficients; both are also
-        in ``info`` (``"push"``, ``"friction"``) when the feature is on."""
+        in ``info`` (``"push"``, ``"friction"``) when the feature is on.
+
+        ``task="locomotion"``: ``command_ranges`` holds the ``(lo, hi)`` of
+        v_x, v_y (m/s) and the yaw rate (rad/s); a command is drawn every
+        ``cmd_interval`` steps (0: once per episode) and is zero with
+        probability ``cmd_zero_prob``.  ``action_scale`` > 0 sends ``home_q +
+        action_scale * a`` (position mode) or ``action_scale * a`` (torque
+        mode) to the simulator.  Reward terms on top of the forward task's
+        (set ``w_forward=0`` to drop that one): ``w_track_lin``, ``w_track_yaw``
+        (``exp(-error^2 / track_sigma)``), ``w_lin_z``, ``w_ang_xy``,
+        ``w_action_rate``, and ``w_air_time`` per touchdown of a contact link
+        (force above ``contact_force_min`` N) after ``air_time_target`` s of
+        flight, for commands faster than ``cmd_min``.  ``env.command``
+        ``[n_worlds, 3]`` (also ``info["command"]``) is the command in force
+        for the next step, the same words as ``obs[:, env.obs_slices["command"]]``.
+        With ``task="forward"`` ``env.command`` is ``None``; command ranges,
+        ``cmd_interval``, ``action_scale`` and ``w_air_time`` are refused there
+        and the other locomotion weights have no effect."""
         torch = _torch()
         if action_mode not in ACTION_MODES:
             raise ValueError(f"unknown action_mode {action_mode!r}; known: {sorted(ACTION_MODES)}")
+        if task not in TASKS:
+            raise ValueError(f"unknown task {task!r}; known: {list(TASKS)}")
+        if len(command_ranges) != 3 or any(len(r) != 2 for r in command_ranges):
+            raise ValueError("command_ranges must hold three (lo, hi) pairs: v_x, v_y, yaw rate")
+        if task == "forward" and (action_scale != 0.0 or cmd_interval != 0 or w_air_time != 0.0 or
+                                  any(float(v) != 0.0 for r in command_ranges for v in r)):
+            raise ValueError('commands, action_scale and the air-time term need task="locomotion"')
         try:
             model_file = get_model_file(model)
         except ValueError:
             model_file = model
         self.action_mode = action_mode
+        self.task = task
         self.n_worlds = n_worlds
         self.device = torch.device("cuda", device)
         self._h = None
@@ -142,17 +184,36 @@ class FloatVecEnv:
         h = ctypes.c_void_p()
         N.check(N.lib().mw_floatenv_create(sim.handle, ctypes.byref(cfg), ctypes.byref(h)), "mw_floatenv_create")
         self._h = h
+        f32 = dict(dtype=torch.float32, device=self.device)
+        self.command = None
+        if task == "locomotion":
+            self.command = torch.zeros((n_worlds, 3), **f32)
+            lc = N.MwFloatLocoConfig(
+                (ctypes.c_float * 3)(*[float(r[0]) for r in command_ranges]),
+                (ctypes.c_float * 3)(*[float(r[1]) for r in command_ranges]),
+                cmd_interval, cmd_zero_prob, cmd_min, action_scale, w_track_lin, w_track_yaw, track_sigma,
+                w_lin_z, w_ang_xy, w_action_rate, w_air_time, air_time_target, contact_force_min)
+            N.check(N.lib().mw_floatenv_locomotion(h, ctypes.byref(lc), ctypes.c_void_p(self.command.data_ptr())),
+                    "mw_floatenv_locomotion")
         no = ctypes.c_int32()
         N.check(N.lib().mw_vecenv_obs_dim(h, ctypes.byref(no)))
         self.obs_dim = no.value
         self.action_dim = n
-        f32 = dict(dtype=torch.float32, device=self.device)
+        nl = len(links)
+        self.obs_slices = {"base": slice(0, 13), "joints": slice(13, 13 + 2 * n),
+                           "contacts": slice(13 + 2 * n, 13 + 2 * n + nl)}
+        if task == "locomotion":
+            nb = 13 + 2 * n + nl
+            self.obs_slices.update(gravity=slice(nb, nb + 3), body_velocity=slice(nb + 3, nb + 9),
+                                   command=slice(nb + 9, nb + 12), last_action=slice(nb + 12, nb + 12 + n))
         self.obs = torch.zeros((n_worlds, self.obs_dim), **f32)
         self.reward = torch.zeros((n_worlds,), **f32)
         self.done = torch.zeros((n_worlds,), dtype=torch.uint8, device=self.device)
         self.terminal_obs = torch.zeros((n_worlds, self.obs_dim), **f32)
         self.push = self.friction = None
         self._info = {"terminal_obs": self.terminal_obs}
+        if self.command is not None:
+            self._info["command"] = self.command
         if push_interval or friction_range is not None:
             lo, hi = (0.0, 0.0) if friction_range is None else friction_range
             if push_interval:
@@ -165,6 +226,9 @@ class FloatVecEnv:
                 None if self.friction is None else ctypes.c_void_p(self.friction.data_ptr())), "mw_floatenv_randomize")
 
     # ------------------------------------------------------------------
+    # what quadruped() / icub() add for task="locomotion" unless the caller sets it
+    LOCOMOTION_DEFAULTS = dict(action_scale=0.25, track_sigma=0.25, air_time_target=0.3)
+
     @classmethod
     def icub(cls, n_worlds: int, **kw) -> "FloatVecEnv":
         """The iCub-class humanoid (BASELINE config 5) from the reference
@@ -176,6 +240,8 @@ class FloatVecEnv:
             return [[p, 0.0, d, -80.0, 80.0, 0.0, 0.0, -1.0] for p, d in icub_pid_gains(names)]
         args = dict(action_mode="position", home_q=icub_posture, home_base=ICUB_POSE, pid_gains=gains,
                     contact_links=("l_foot", "r_foot"), z_min=0.3, max_tilt=1.0, pgs_iters=50)
+        if kw.get("task") == "locomotion":
+            args.update(cls.LOCOMOTION_DEFAULTS)
         args.update(kw)
         return cls("icub", n_worlds, **args)
 
@@ -185,6 +251,8 @@ class FloatVecEnv:
         args = dict(action_mode="position", home_q=[0.6, -1.2] * 4, home_base=(0.0, 0.0, 0.45, 1.0, 0.0, 0.0, 0.0),
                     pid_gains=[[400.0, 0.0, 10.0, -60.0, 60.0, 0.0, 0.0, -1.0]] * 8,
                     contact_links=("shank_fl", "shank_fr", "shank_hl", "shank_hr"), z_min=0.15, max_tilt=1.0)
+        if kw.get("task") == "locomotion":
+            args.update(cls.LOCOMOTION_DEFAULTS)
         args.update(kw)
         return cls("quadruped", n_worlds, **args)
 

@@ -106,6 +106,27 @@ class MwFloatRandConfig(ctypes.Structure):
     ]
 
 
+class MwFloatLocoConfig(ctypes.Structure):
+    """mw_float_loco_config (include/mwstep.h)."""
+    _fields_ = [
+        ("cmd_lo", ctypes.c_float * 3),
+        ("cmd_hi", ctypes.c_float * 3),
+        ("cmd_interval", ctypes.c_int32),
+        ("cmd_zero_prob", ctypes.c_float),
+        ("cmd_min", ctypes.c_float),
+        ("action_scale", ctypes.c_float),
+        ("w_track_lin", ctypes.c_float),
+        ("w_track_yaw", ctypes.c_float),
+        ("track_sigma", ctypes.c_float),
+        ("w_lin_z", ctypes.c_float),
+        ("w_ang_xy", ctypes.c_float),
+        ("w_action_rate", ctypes.c_float),
+        ("w_air_time", ctypes.c_float),
+        ("air_time_target", ctypes.c_float),
+        ("contact_force_min", ctypes.c_float),
+    ]
+
+
 # (name, restype, argtypes) of every symbol in include/mwstep.h
 _P = ctypes.c_void_p
 _I = ctypes.c_int32
@@ -198,6 +219,7 @@ SIGNATURES = [
     ("mw_vecenv_physics", ctypes.c_int, [_P, _P, _P]),
     ("mw_floatenv_create", ctypes.c_int, [_P, ctypes.POINTER(MwFloatTaskConfig), ctypes.POINTER(_P)]),
     ("mw_floatenv_randomize", ctypes.c_int, [_P, ctypes.POINTER(MwFloatRandConfig), _P, _P]),
+    ("mw_floatenv_locomotion", ctypes.c_int, [_P, ctypes.POINTER(MwFloatLocoConfig), _P]),
 ]
 
 # include/mwscene.h

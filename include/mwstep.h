@@ -514,6 +514,63 @@ typedef struct {
 } mw_float_rand_config;
 int mw_floatenv_randomize(mw_vecenv* env, const mw_float_rand_config* cfg, float* push_dev, float* friction_dev);
 
+/* Velocity-command locomotion task of a floating-base env, sampled and scored
+ * on the device.  Call it after mw_floatenv_create and before the first
+ * mw_vecenv_reset (MW_ESTATE after it, or on another kind of env); it combines
+ * freely with mw_floatenv_randomize, in either order.  The step stays three
+ * launches without host copies or synchronisation.  A refused call leaves the
+ * env as it was.
+ *   obs      the row grows to 25 + 3 n_dofs + n_contact_links words
+ *            (mw_vecenv_obs_dim returns the new width): behind the words of
+ *            the plain env come the projected gravity (world -z in the body
+ *            frame, 3), the body-frame linear (3) and angular (3) velocity of
+ *            the base, the command (v_x, v_y, yaw rate) in force for the next
+ *            step (3) and the raw action just applied (n_dofs, zeros after a
+ *            reset)
+ *   command  a pure function of (seed, global world, episode, k), k = steps
+ *            taken / cmd_interval (0 with cmd_interval 0, k < 2^30): Philox
+ *            block 0xC0000000 | k of the counter mw_floatenv_randomize
+ *            describes; r[0..2] give U(cmd_lo[i], cmd_hi[i]), and the command
+ *            is zero where (r[3] >> 8) 2^-24 < cmd_zero_prob.  The reward of a
+ *            step uses the command the previous observation showed; the
+ *            observation after it shows the command of step count t + 1
+ *            (terminal_obs: the one the finished episode would have had), a
+ *            reset observation command 0 of the new episode.
+ *   actions  kept raw for the observation and the action-rate term; with
+ *            action_scale > 0 the run receives home_q[d] + action_scale a_d
+ *            (position mode, one fused multiply-add) or action_scale a_d
+ *            (torque mode).  sum a^2 and the non-finite test use the raw action.
+ *   reward   the four terms of mw_floatenv_create, and with v, w the
+ *            body-frame linear and angular velocity and c the command
+ *              + w_track_lin exp(-((c_x - v_x)^2 + (c_y - v_y)^2) / track_sigma)
+ *              + w_track_yaw exp(-(c_yaw - w_z)^2 / track_sigma)
+ *              - w_lin_z v_z^2 - w_ang_xy (w_x^2 + w_y^2)
+ *              - w_action_rate sum (a_t - a_{t-1})^2        (a_{t-1} = 0 on an
+ *                episode's first step)
+ *              + w_air_time sum_j [touchdown_j] (air_steps_j env_dt -
+ *                air_time_target) where c_x^2 + c_y^2 > cmd_min^2
+ *            Contact link j is in contact when its observed z force exceeds
+ *            contact_force_min; air_steps_j counts the steps without contact,
+ *            is paid and zeroed on the first step with contact after a flight
+ *            and zeroed on reset; env_dt = steps_per_run step_size.
+ * command_dev float32 [n_worlds, 3] is a caller-owned device buffer (may be
+ * NULL) that must outlive the env: every step and reset writes the command
+ * words of obs into it. */
+typedef struct {
+    float cmd_lo[3], cmd_hi[3];     /* v_x, v_y (m/s), yaw rate (rad/s); lo <= hi */
+    int32_t cmd_interval;           /* steps between draws; 0 = once per episode  */
+    float cmd_zero_prob;            /* in [0, 1]                                  */
+    float cmd_min;                  /* m/s                                        */
+    float action_scale;             /* >= 0; 0 = raw actions                      */
+    float w_track_lin, w_track_yaw;
+    float track_sigma;              /* > 0                                        */
+    float w_lin_z, w_ang_xy, w_action_rate;
+    float w_air_time;               /* != 0 needs contact links                   */
+    float air_time_target;          /* s                                          */
+    float contact_force_min;        /* N                                          */
+} mw_float_loco_config;
+int mw_floatenv_locomotion(mw_vecenv* env, const mw_float_loco_config* cfg, float* command_dev);
+
 #ifdef __cplusplus
 }
 #endif

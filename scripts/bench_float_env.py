@@ -22,6 +22,12 @@ second env with pushes and friction randomisation on (mw_floatenv_randomize;
 the run then takes the wave kernel's wrench path, and the env kernels move 28
 more bytes per world), and reports env_rand - env.
 
+--task locomotion adds env_loco to the alternation: the step of another env
+with the velocity-command task on (mw_floatenv_locomotion: the LOCO instances
+of both env kernels, 12 + n more observation words and the kept action row
+per world), fed zero actions -- the home posture through action_scale, the
+same physics as env -- and reports env_loco - env.
+
 Not a bench.py leg.  Prints one JSON line per model."""
 
 import argparse
@@ -33,6 +39,9 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # --randomize: a push of 5 steps every 50, and a new friction coefficient per episode
 RANDOMIZE = dict(push_interval=50, push_steps=5, push_force=30.0, push_torque=5.0, friction_range=(0.5, 1.25))
+# --task locomotion: commands redrawn every 100 steps, every reward term on
+LOCOMOTION = dict(task="locomotion", command_ranges=((-1.0, 1.0), (-0.5, 0.5), (-1.0, 1.0)), cmd_interval=100,
+                  cmd_zero_prob=0.1, cmd_min=0.1, w_lin_z=2.0, w_ang_xy=0.05, w_action_rate=0.01, w_air_time=1.0)
 sys.path.insert(0, os.path.join(ROOT, "gym-ignition_amd", "python"))
 
 
@@ -108,6 +117,13 @@ def measure(torch, args, model, W):
             rand = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0, **RANDOMIZE)
             rand.reset()
         graphs["env_rand"] = capture(torch, stream, lambda: rand.step_raw(actions.data_ptr()), args.warmup)
+    loco = None
+    if args.task == "locomotion":
+        with torch.cuda.stream(stream):
+            loco = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0, **LOCOMOTION)
+            loco.reset()
+            zeros = torch.zeros((W, loco.action_dim), dtype=torch.float32, device=loco.device)
+        graphs["env_loco"] = capture(torch, stream, lambda: loco.step_raw(zeros.data_ptr()), args.warmup)
     times = {k: [] for k in graphs}
     for _ in range(args.rounds):
         for k, g in graphs.items():
@@ -133,6 +149,15 @@ def measure(torch, args, model, W):
                     "friction_range_seen": [round(float(rand.friction.min()), 4), round(float(rand.friction.max()), 4)],
                     "extra_bytes_per_world": 28})
         rand.close()
+    if loco is not None:
+        zl = loco.sim.base_pose()[:, 2]
+        out.update({"env_loco_step_us": round(med["env_loco"], 3),
+                    "loco_minus_env_us": round(med["env_loco"] - med["env"], 3),
+                    "loco_minus_env_over_floor": round((med["env_loco"] - med["env"]) / med["floor"], 3),
+                    "loco_obs_dim": loco.obs_dim,
+                    "loco_bytes_moved_by_env_kernels": W * (loco.obs_dim + 3 * loco.action_dim + 3) * 4,
+                    "loco_base_z_range_after": [round(float(zl.min()), 4), round(float(zl.max()), 4)]})
+        loco.close()
     env.close()
     sim.close()
     return out
@@ -147,6 +172,8 @@ def main():
     p.add_argument("--quadruped-worlds", type=int, default=4096)
     p.add_argument("--randomize", action="store_true",
                    help="also time an env with pushes and friction randomisation on (env_rand)")
+    p.add_argument("--task", choices=("forward", "locomotion"), default="forward",
+                   help="locomotion: also time an env with the velocity-command task on (env_loco)")
     args = p.parse_args()
     if args.replays < 200:
         p.error("--replays must be >= 200")

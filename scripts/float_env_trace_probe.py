@@ -1,0 +1,46 @@
+#!/usr/bin/env python3
+"""Workload for a kernel trace of the floating-base env's two task kernels:
+300 eager steps of a plain FloatVecEnv and of one with the locomotion task on
+(the configuration of bench_float_env.py --task locomotion), alternating, for
+the iCub at 512 worlds and the quadruped at 4,096.  Both hold the home
+posture, so the run kernel does the same work in either.
+
+    rocprofv3 --kernel-trace --stats -d OUT -o run --output-format csv -- python3 scripts/float_env_trace_probe.py
+
+The dispatches of float_env_action_kernel<LOCO> and float_env_post_kernel<RAND,
+PUSH, LOCO> in OUT/run_kernel_trace.csv, grouped by kernel name and grid size
+(2,048 threads: the iCub's 8 blocks; 16,384: the quadruped's 64), give the
+cost of each kernel with and without the task (profiles/float_loco/)."""
+
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "gym-ignition_amd", "python"))
+sys.path.insert(0, os.path.join(ROOT, "scripts"))
+
+
+def main():
+    import numpy as np
+    import torch
+    from bench_float_env import LOCOMOTION
+    from mwstep import FloatVecEnv
+    if not torch.cuda.is_available():
+        sys.exit("float_env_trace_probe.py needs the GPU")
+    for model, W in (("icub", 512), ("quadruped", 4096)):
+        plain = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0)
+        loco = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0, **LOCOMOTION)
+        plain.reset()
+        loco.reset()
+        hold = torch.from_numpy(np.tile(plain.home_q, (W, 1))).to(plain.device)
+        zeros = torch.zeros((W, loco.action_dim), dtype=torch.float32, device=loco.device)
+        for _ in range(300):
+            plain.step_raw(hold.data_ptr())
+            loco.step_raw(zeros.data_ptr())
+        torch.cuda.synchronize()
+        plain.close()
+        loco.close()
+
+
+if __name__ == "__main__":
+    main()
