@@ -11,7 +11,9 @@
 // the post launch's PUSH instance reports the push the run applied and writes
 // the next step's into the run kernel's wrench array, its RAND instance draws
 // the friction of every episode it starts into the simulator's per-world
-// array (T.rand.mu).  The locomotion task (mw_floatenv_locomotion) is the LOCO
+// array (T.rand.mu), its INERT instance (mw_floatenv_inertia) the link masses
+// and the base payload into the simulator's per-world link parameters
+// (T.inertia.wpar).  The locomotion task (mw_floatenv_locomotion) is the LOCO
 // instance of both env kernels: the action launch keeps the raw action and the
 // action-rate sum and writes the scaled command, the post launch appends the
 // body-frame block of the observation, draws the velocity commands and adds
@@ -38,6 +40,9 @@ namespace dev {
 constexpr int kEnvTile = 64;      // worlds per block (lane = world)
 constexpr int kEnvThreads = 256;  // 4 waves share the tile's columns / rows
 constexpr int kEnvWaves = kEnvThreads / 64;
+static_assert(kFtWparBody0 == kWparBaseWords + kWparHeadWords && kFtBodyWords * 4 == sizeof(BodyF) &&
+                  kFtBodyInertial * 4 == offsetof(BodyF, mass),
+              "float_task.hpp restates the layout of RunArgs::wpar");
 
 // actions [W, n] -> out [n][W] (SimDev::cmd or ptgt), and sum_i a_i^2 per
 // world for the reward (asq [W]).  The value stored is the float32 the host
@@ -142,7 +147,19 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_action_kernel(const flo
 // link's contact force also step its air-time counter and leave the touchdown
 // payment in LDS for wave 0's reward.  A reset zeroes the kept action row and
 // the air counters.
-template <bool RAND, bool PUSH, bool LOCO>
+// INERT (mw_floatenv_inertia, T.inertia): a reset also draws the inertial
+// words of the episode it starts -- link k (0 = the base, 1 + i = body i)
+// scaled by U(mass_lo, mass_hi) from word k % 4 of block kFtScaleBlock | k / 4,
+// then the payload of block kFtPayloadBlock added to the base
+// (float_task.hpp; a feature that is off is skipped) -- from the nominal words
+// (P, the shared ChainF; T.inertia.base0) into the world's record of the run
+// kernel's per-world link parameters (T.inertia.wpar: the base's ten words,
+// words 16..25 of each BodyF), T.inertia.inertial_out and, the draws
+// themselves, T.inertia.draw_out; the next run reads the record together with
+// the pending reset.  The blocks of four links go round the
+// waves starting at wave 1, so wave 0's chain takes one only from the 13th
+// link on.
+template <bool RAND, bool PUSH, bool LOCO, bool INERT>
 __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const ChainF* __restrict__ P, FloatTaskF T,
                                                                      SimDev S, FreeDev D, VecDev V,
                                                                      const float* __restrict__ asq,
@@ -350,6 +367,53 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
             T.rand.mu[w] = mu;
             if (T.rand.friction_out) T.rand.friction_out[w] = mu;
         }
+        if constexpr (INERT) {
+            const FloatInertiaF& I = T.inertia;
+            const uint32_t g = T.world_offset + static_cast<uint32_t>(w);
+            const bool scale = I.mass_hi > 0.f, payload = I.payload_hi > 0.f;
+            float* __restrict__ rec = I.wpar + static_cast<size_t>(w) * I.stride;
+            float* __restrict__ out = I.inertial_out ? I.inertial_out + static_cast<size_t>(w) * (n + 1) * 10 : nullptr;
+            float* __restrict__ draw = I.draw_out ? I.draw_out + static_cast<size_t>(w) * (n + 5) : nullptr;
+            for (int b = (wave + kEnvWaves - 1) % kEnvWaves; 4 * b <= n; b += kEnvWaves) {
+                uint32_t r[4] = {0u, 0u, 0u, 0u};
+                if (scale) philox(T.seed_lo, T.seed_hi, g, episode, r, ft_scale_block(4 * b));
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const int k = 4 * b + j;
+                    if (k <= n) {
+                        const float* __restrict__ nom = k ? &P->b[k - 1].mass : I.base0;
+                        float w0[10], wd[10];
+#pragma unroll
+                        for (int e = 0; e < 10; ++e) wd[e] = w0[e] = nom[e];
+                        const float s = scale ? unif(r[j], I.mass_lo, I.mass_hi) : 1.f;
+                        if (scale) ft_inertia_scale(w0, s, wd);
+                        if (draw) draw[k] = s;
+                        if (k == 0) {
+                            float mp = 0.f, pp[3] = {0.f, 0.f, 0.f};
+                            if (payload) {
+                                uint32_t rp[4];
+                                philox(T.seed_lo, T.seed_hi, g, episode, rp, kFtPayloadBlock);
+                                mp = unif(rp[0], I.payload_lo, I.payload_hi);
+#pragma unroll
+                                for (int e = 0; e < 3; ++e) pp[e] = unif(rp[1 + e], -I.payload_box[e], I.payload_box[e]);
+                                ft_inertia_payload(wd, mp, pp);
+                            }
+                            if (draw) {
+                                draw[n + 1] = mp;
+#pragma unroll
+                                for (int e = 0; e < 3; ++e) draw[n + 2 + e] = pp[e];
+                            }
+                        }
+                        float* __restrict__ dst = k ? rec + kFtWparBody0 + (k - 1) * kFtBodyWords + kFtBodyInertial : rec;
+#pragma unroll
+                        for (int e = 0; e < 10; ++e) {
+                            dst[e] = wd[e];
+                            if (out) out[k * 10 + e] = wd[e];
+                        }
+                    }
+                }
+            }
+        }
         for (int j = wave; j < T.n_links; j += kEnvWaves) {
             row[13 + 2 * n + j] = 0.f;
             if constexpr (LOCO) T.loco.air_steps[j * Ws + w] = 0u;
@@ -414,18 +478,23 @@ hipError_t launch_float_env_post(const ChainF* P, const FloatTaskF& T, const Sim
     // links) 64 x 177 words = 45 KB, with the kernel's 3.3 KB of static LDS
     // still inside the 64 KB a block gets without asking for more.
     const bool rand = T.rand.friction_hi > 0.f, push = T.rand.push_interval > 0u, loco = T.loco.on != 0u;
-#define MW_POST(R_, P_, L_)                                                                                     \
-    hipLaunchKernelGGL((dev::float_env_post_kernel<R_, P_, L_>), grid, block, lds, st, P, T, S, D, V, asq, obs, \
+    const bool inert = T.inertia.wpar != nullptr;
+#define MW_POST(R_, P_, L_, I_)                                                                                     \
+    hipLaunchKernelGGL((dev::float_env_post_kernel<R_, P_, L_, I_>), grid, block, lds, st, P, T, S, D, V, asq, obs, \
                        reward, done, term_obs, n, W, reset_all)
-#define MW_POST_RP(L_)                       \
-    if (rand && push) MW_POST(true, true, L_);   \
-    else if (rand) MW_POST(true, false, L_);     \
-    else if (push) MW_POST(false, true, L_);     \
-    else MW_POST(false, false, L_)
-    if (loco) {
-        MW_POST_RP(true);
+#define MW_POST_RP(L_, I_)                           \
+    if (rand && push) MW_POST(true, true, L_, I_);   \
+    else if (rand) MW_POST(true, false, L_, I_);     \
+    else if (push) MW_POST(false, true, L_, I_);     \
+    else MW_POST(false, false, L_, I_)
+    if (loco && inert) {
+        MW_POST_RP(true, true);
+    } else if (loco) {
+        MW_POST_RP(true, false);
+    } else if (inert) {
+        MW_POST_RP(false, true);
     } else {
-        MW_POST_RP(false);
+        MW_POST_RP(false, false);
     }
 #undef MW_POST_RP
 #undef MW_POST

@@ -5,7 +5,9 @@
 // tests/host_float_task/harness.cpp builds the same code with g++ against
 // numpy fp64.  The Philox reset sampling stays in rng.hpp (device only); the
 // integer arithmetic of the push schedule (mw_floatenv_randomize) is here too,
-// built by tests/host_float_rand/harness.cpp, and so is the arithmetic of the
+// built by tests/host_float_rand/harness.cpp, the inertial words of the
+// inertia randomisation (mw_floatenv_inertia: mass scale, payload), built by
+// tests/host_float_inertia/harness.cpp, and so is the arithmetic of the
 // locomotion task (mw_floatenv_locomotion: commands, projected gravity, the
 // air-time counter, the extra reward terms), built by
 // tests/host_float_loco/harness.cpp.
@@ -71,6 +73,23 @@ struct FloatLocoF {
     float* command_out;          // [W, 3] the command in force for the next step (caller's, may be null)
 };
 
+// Inertia randomisation of the floating-base env (mw_floatenv_inertia): link
+// mass scales and a payload on the base, each off when its `hi` is zero.
+struct FloatInertiaF {
+    float mass_lo, mass_hi;        // s ~ U(lo, hi) per link and episode; on when hi > 0
+    float payload_lo, payload_hi;  // m_p ~ U(lo, hi) kg per episode; on when hi > 0
+    float payload_box[3];          // p ~ U(-box, box) m, base frame
+    int32_t stride;                // words between two worlds' records in wpar
+    float base0[10];               // the base's nominal inertial words (FloatF's first ten)
+    float* wpar;                   // the simulator's per-world link parameters (mw_sim::d_wpar, RunArgs::wpar)
+    float* inertial_out;           // [W, n + 1, 10] the words of the current episode (caller's, may be null)
+    float* draw_out;               // [W, n + 5] the episode's draws: s_0 .. s_n, m_p, p xyz (caller's, may be null)
+};
+constexpr int kFtWparBody0 = 16 + 8;  // words of a record before its first BodyF (kernels.hpp)
+constexpr int kFtBodyWords = 40, kFtBodyInertial = 16;  // BodyF words; its ten inertial words start here
+constexpr uint32_t kFtScaleBlock = 0x40000100u;    // | k / 4, word k % 4: scale of link k (0 = the base), k <= 48
+constexpr uint32_t kFtPayloadBlock = 0x40000180u;  // r[0]: payload mass, r[1..3]: its position
+
 // Task description of the floating-base env (kernel argument, by value).
 struct FloatTaskF {
     int32_t action_mode;     // 0 torque (SimDev::cmd), 1 position (SimDev::ptgt)
@@ -87,6 +106,7 @@ struct FloatTaskF {
     float home_q[kMaxBodies];
     FloatRandF rand;
     FloatLocoF loco;
+    FloatInertiaF inertia;
 };
 
 namespace dev {
@@ -156,13 +176,66 @@ __device__ __forceinline__ float ft_reward(const FloatTaskF& T, bool terminated,
     return (terminated ? 0.f : T.alive_bonus) + T.w_forward * vx - T.w_action * sum_a2 - T.w_pose * sum_pose2;
 }
 
-// ---- locomotion task (FloatLocoF) ----
-
 // rng.hpp's unif(), restated here so that the host harnesses build it:
 // lo + (hi - lo) (x >> 8) 2^-24.
 __device__ __forceinline__ float ft_unif(uint32_t x, float lo, float hi) {
     return lo + (hi - lo) * (static_cast<float>(x >> 8) * (1.f / 16777216.f));
 }
+
+// ---- inertia randomisation (FloatInertiaF) ----
+// A link's ten inertial words: mass, com xyz, Io xx yy zz xy xz yz about the
+// link origin.  Every fused operation is an explicit fmaf and every other
+// product, sum or quotient is rounded on its own: the device build contracts
+// a * b + c wherever it finds one, across statements and inlined calls too, so
+// both functions switch contraction off for their own operations.  The words
+// are then defined values, the same from hipcc and from a host compiler.
+#if defined(__clang__)
+#define MW_FT_NO_CONTRACT _Pragma("clang fp contract(off)")
+#else
+#define MW_FT_NO_CONTRACT
+#endif
+
+// mass = s mass0, Io[k] = s Io0[k], the centre of mass kept: 7 roundings.
+__device__ __forceinline__ void ft_inertia_scale(const float (&w0)[10], float s, float (&w)[10]) {
+    MW_FT_NO_CONTRACT
+    w[0] = s * w0[0];
+#pragma unroll
+    for (int k = 1; k < 4; ++k) w[k] = w0[k];
+#pragma unroll
+    for (int k = 4; k < 10; ++k) w[k] = s * w0[k];
+}
+
+// A point mass mp at p (link frame) joins the link, in place:
+//   m' = m + mp;  com' = (m com + mp p) / m';  Io' = Io + mp (|p|^2 1 - p p^T)
+// with |p|^2 - p_x^2 taken as p_y^2 + p_z^2 (no cancellation).
+__device__ __forceinline__ void ft_inertia_payload(float (&w)[10], float mp, const float (&p)[3]) {
+    MW_FT_NO_CONTRACT
+    const float m = w[0];
+    const float m1 = m + mp;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float mc = m * w[1 + k];
+        const float num = fmaf(mp, p[k], mc);
+        w[1 + k] = num / m1;
+    }
+    const float xx = p[0] * p[0], yy = p[1] * p[1], zz = p[2] * p[2];
+    const float xy = p[0] * p[1], xz = p[0] * p[2], yz = p[1] * p[2];
+    const float syz = yy + zz, sxz = xx + zz, sxy = xx + yy;
+    w[0] = m1;
+    w[4] = fmaf(mp, syz, w[4]);
+    w[5] = fmaf(mp, sxz, w[5]);
+    w[6] = fmaf(mp, sxy, w[6]);
+    w[7] = fmaf(-mp, xy, w[7]);
+    w[8] = fmaf(-mp, xz, w[8]);
+    w[9] = fmaf(-mp, yz, w[9]);
+}
+
+#undef MW_FT_NO_CONTRACT
+
+// Philox block of link k's scale (k = 0 the base, 1 + i body i); its word is k % 4
+__device__ __forceinline__ uint32_t ft_scale_block(int k) { return kFtScaleBlock | static_cast<uint32_t>(k >> 2); }
+
+// ---- locomotion task (FloatLocoF) ----
 
 // The command schedule is a pure function of (seed, global world, episode, t),
 // t the steps already taken in the episode: command k = t / cmd_interval (0

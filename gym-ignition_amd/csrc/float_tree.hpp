@@ -177,6 +177,18 @@ struct Chol6 {
     }
 };
 
+// bw: the base's ten inertial words -- mass, com[3], Io[6] --, FloatF's first
+// ten or a world's own (RunArgs::wpar)
+__device__ __forceinline__ SI rigid_base(const float* __restrict__ bw) {
+    SI I;
+    const float m = bw[0], cx = bw[1], cy = bw[2], cz = bw[3];
+    I.A = {bw[4], bw[5], bw[6], bw[7], bw[8], bw[9]};
+    I.B.m[0] = 0.f;     I.B.m[1] = -m * cz; I.B.m[2] = m * cy;
+    I.B.m[3] = m * cz;  I.B.m[4] = 0.f;     I.B.m[5] = -m * cx;
+    I.B.m[6] = -m * cy; I.B.m[7] = m * cx;  I.B.m[8] = 0.f;
+    I.C = {m, m, m, 0.f, 0.f, 0.f};
+    return I;
+}
 __device__ __forceinline__ SI rigid_base(const FloatF& F) {
     SI I;
     const float m = F.mass, cx = F.com[0], cy = F.com[1], cz = F.com[2];

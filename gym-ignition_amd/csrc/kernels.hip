@@ -403,13 +403,20 @@ __device__ __forceinline__ float dof_force(const ChainF* __restrict__ P, const S
     return tau;
 }
 
-template <int MAXN, bool CONS, bool WMU>
-__global__ void __launch_bounds__(64, 1) wave_run_kernel(const ChainF* __restrict__ P, const FloatF* __restrict__ F,
+template <int MAXN, bool CONS, bool WMU, bool WPAR>
+__global__ void __launch_bounds__(64, 1) wave_run_kernel(const ChainF* __restrict__ Ps, const FloatF* __restrict__ F,
                                                       int N, SimDev S, FreeDev D, const PidF* __restrict__ pid,
                                                       int W, RunArgs A, int want_contacts, int* __restrict__ overflow) {
     MW_PROF_T(tk0);
     const int w = xcd_block();  // XCD-aware (xcd.hpp): neighbouring worlds share state lines
     const int lane = lane_id();
+    // WPAR: per-world link parameters (mw_set_link_params).  w is wave-uniform,
+    // so "this world's parameters" is another base address for the same scalar
+    // loads: P is the world's own body block, bw its base's ten inertial words
+    // (RunArgs::wpar); without it the shared ChainF and FloatF's first ten words
+    const float* __restrict__ rec = WPAR ? A.wpar + static_cast<size_t>(w) * A.wpar_stride : nullptr;
+    const ChainF* __restrict__ P = WPAR ? reinterpret_cast<const ChainF*>(rec + kWparBaseWords) : Ps;
+    const float* __restrict__ bw = WPAR ? rec : &F->mass;
     __shared__ WaveWorld<MAXN> L;
     // Every load of the prologue is issued before any is used: the reset flags
     // used to gate the warm-record and reset-value loads, two dependent round
@@ -501,7 +508,8 @@ __global__ void __launch_bounds__(64, 1) wave_run_kernel(const ChainF* __restric
             MW_PROF_T(tb);
             MW_PROF_ACC(0, ta, tb);
             active = wave_step<MAXN, CONS>(P, F, N, base, L, A.dt, A.pgs_iters, A.pgs_tol, A.warm != 0,
-                                           A.lcp_solves, L.qdd, &ovf, &unconv, prof, A.wrenches != 0, mu_w);
+                                           A.lcp_solves, L.qdd, &ovf, &unconv, prof, A.wrenches != 0, mu_w,
+                                           bw);
             MW_PROF_T(tc);
             MW_PROF_ACC(7, ta, tc);
         }
@@ -766,19 +774,19 @@ template <int MAXN>
 static void wave_launch(bool cons, dim3 grid, dim3 block, hipStream_t st, const ChainF* P, const FloatF* F,
                         int n, const SimDev& S, const FreeDev& D, const PidF* pid, int W, const RunArgs& a,
                         int contacts, int* overflow) {
-    const bool wmu = a.mu != nullptr;
-    if (cons && wmu)
-        hipLaunchKernelGGL((dev::wave_run_kernel<MAXN, true, true>), grid, block, 0, st, P, F, n, S, D, pid, W, a,
-                           contacts, overflow);
-    else if (cons)
-        hipLaunchKernelGGL((dev::wave_run_kernel<MAXN, true, false>), grid, block, 0, st, P, F, n, S, D, pid, W, a,
-                           contacts, overflow);
-    else if (wmu)
-        hipLaunchKernelGGL((dev::wave_run_kernel<MAXN, false, true>), grid, block, 0, st, P, F, n, S, D, pid, W, a,
-                           contacts, overflow);
-    else
-        hipLaunchKernelGGL((dev::wave_run_kernel<MAXN, false, false>), grid, block, 0, st, P, F, n, S, D, pid, W, a,
-                           contacts, overflow);
+    // WPAR implies WMU (sim.cpp allocates the friction array with the link
+    // parameters): 6 more instances, not 12
+    const bool wmu = a.mu != nullptr, wpar = a.wpar != nullptr && wmu;
+#define MW_WAVE(C_, M_, P_)                                                                                         \
+    hipLaunchKernelGGL((dev::wave_run_kernel<MAXN, C_, M_, P_>), grid, block, 0, st, P, F, n, S, D, pid, W, a, contacts, \
+                       overflow)
+    if (cons && wpar) MW_WAVE(true, true, true);
+    else if (cons && wmu) MW_WAVE(true, true, false);
+    else if (cons) MW_WAVE(true, false, false);
+    else if (wpar) MW_WAVE(false, true, true);
+    else if (wmu) MW_WAVE(false, true, false);
+    else MW_WAVE(false, false, false);
+#undef MW_WAVE
 }
 
 hipError_t launch_wave_run(const ChainF* P, int n, int depth, bool cons, const FloatF* F, const SimDev& S,
@@ -790,7 +798,8 @@ hipError_t launch_wave_run(const ChainF* P, int n, int depth, bool cons, const F
     // when the simulator has the array: in the shared one the extra live
     // pointer moved the register allocation and cost the quadruped leg 1 %
     // (DESIGN 3.6b), so a simulator without the array (RunArgs::mu null) runs the
-    // kernel as it was
+    // kernel as it was.  The per-world link parameters (RunArgs::wpar) are a
+    // fourth template argument for the same reason.
     if (n <= 16 && depth <= dev::WaveWorld<16>::kDepth)
         wave_launch<16>(cons, grid, block, st, P, F, n, S, D, pid, W, a, contacts, overflow);
     else if (n <= 32)

@@ -72,7 +72,27 @@ struct RunArgs {
     // [W] per-world ground friction in device memory (wave kernel,
     // mw_set_ground_friction), or null: every world takes FloatF::mu
     const float* mu;
+    // per-world link parameters in device memory (wave kernel,
+    // mw_set_link_params), or null: every world takes the shared ChainF / FloatF.
+    // One record of wpar_stride words per world, wave-uniform like mu:
+    //   [0, 10)   the base's inertial words, as FloatF's first ten: mass,
+    //             com[3], Io[6] about the origin (padded to kWparBaseWords)
+    //   [16, ..)  the world's body block, stored compactly: the ChainF header
+    //             (kWparHeadWords) and n BodyF, not the 48-body struct
+    // Only the inertial words differ between worlds; everything else in the
+    // body block (joint frames, limits, effort, damping) is a copy of the
+    // shared ChainF, and every setter that rewrites the shared block
+    // (mw_set_joint_param, mw_set_gravity: upload_params) rewrites all copies,
+    // keeping each world's inertial words.  FloatF (ground, shapes, gravity,
+    // topology tables) is not duplicated and keeps one owner.  With wpar set the
+    // kernel runs its WPAR instances, which imply the per-world friction read:
+    // mu is then non-null as well.
+    const float* wpar;
+    int wpar_stride;
 };
+constexpr int kWparBaseWords = 16;
+constexpr int kWparHeadWords = 8;  // offsetof(ChainF, b) / 4
+constexpr int wpar_stride_words(int n) { return kWparBaseWords + kWparHeadWords + 40 * n; }
 
 // Task description for the device-side env (see sim.cpp for the sources).
 struct TaskF {

@@ -110,7 +110,85 @@ int pull_ground_friction(mw_sim* s) {
     return MW_OK;
 }
 
+// One world's link parameter record from the shared blocks (kernels.hpp
+// RunArgs::wpar): the base's ten inertial words, the ChainF header, n BodyF.
+static void fill_link_record(const mw_sim* s, float* rec) {
+    std::memset(rec, 0, mw::kWparBaseWords * sizeof(float));
+    std::memcpy(rec, &s->h_float.mass, 10 * sizeof(float));
+    std::memcpy(rec + mw::kWparBaseWords, &s->h_params, mw::kWparHeadWords * sizeof(float));
+    std::memcpy(rec + mw::kWparBaseWords + mw::kWparHeadWords, s->h_params.b,
+                static_cast<size_t>(s->n) * sizeof(mw::BodyF));
+}
+static_assert(offsetof(mw::ChainF, b) == mw::kWparHeadWords * sizeof(float), "ChainF header words");
+static_assert(offsetof(mw::FloatF, Io) == 4 * sizeof(float) && offsetof(mw::FloatF, g) == 10 * sizeof(float),
+              "FloatF starts with the base's ten inertial words");
+static_assert(offsetof(mw::BodyF, mass) == 16 * sizeof(float) && offsetof(mw::BodyF, damping) == 26 * sizeof(float),
+              "BodyF words 16..25 are the body's ten inertial words");
+
+// the ten inertial words of `link` (-1 = the base) inside a world's record
+static float* link_words(float* rec, int link) {
+    return link < 0 ? rec : rec + mw::kWparBaseWords + mw::kWparHeadWords + 40 * link + 16;
+}
+
+// The per-world link parameters, every world at the model's nominal words:
+// allocate and fill, then publish (a failed call leaves the simulator as it
+// was).  The friction array comes with them: the kernel's per-world-parameter
+// instances imply the per-world friction read.
+int alloc_link_params(mw_sim* s) {
+    if (s->d_wpar) return MW_OK;
+    const int stride = mw::wpar_stride_words(s->n);
+    const size_t W = static_cast<size_t>(s->W), words = W * stride;
+    mw::dev_ptr<float[]> d;
+    MW_HIP(mw::dev_alloc(d, words * sizeof(float)));
+    std::vector<float> h(words);
+    fill_link_record(s, h.data());
+    for (size_t w = 1; w < W; ++w) std::memcpy(h.data() + w * stride, h.data(), stride * sizeof(float));
+    MW_HIP(hipMemcpyAsync(d.get(), h.data(), words * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    MW_HIP(hipStreamSynchronize(s->stream));  // the mirror is pageable and rewritten by the setter
+    if (int rc = alloc_ground_friction(s)) return rc;
+    s->h_wpar = std::move(h);
+    s->wpar_stride = stride;
+    s->d_wpar = std::move(d);
+    return MW_OK;
+}
+
+// device -> host mirror of the link parameter records (an env's kernels wrote them)
+int pull_link_params(mw_sim* s) {
+    if (!s->d_wpar) return MW_OK;
+    MW_HIP(hipMemcpyAsync(s->h_wpar.data(), s->d_wpar.get(), s->h_wpar.size() * sizeof(float), hipMemcpyDeviceToHost,
+                          s->stream));
+    MW_HIP(hipStreamSynchronize(s->stream));
+    return MW_OK;
+}
+
 namespace {
+
+// host mirror -> device, worlds [w0, w0 + nw)
+int upload_link_params(mw_sim* s, int32_t w0, int32_t nw) {
+    if (nw <= 0) return MW_OK;
+    const size_t stride = static_cast<size_t>(s->wpar_stride);
+    MW_HIP(hipMemcpyAsync(s->d_wpar.get() + w0 * stride, s->h_wpar.data() + w0 * stride, nw * stride * sizeof(float),
+                          hipMemcpyHostToDevice, s->stream));
+    MW_HIP(hipStreamSynchronize(s->stream));  // the pageable mirror may be rewritten at once
+    return MW_OK;
+}
+
+// The shared parameter blocks were rebuilt (upload_params): every world's
+// record takes the new joint words and keeps its own inertial words.
+int refresh_link_params(mw_sim* s) {
+    if (!s->d_wpar) return MW_OK;
+    if (s->env_inertia)
+        if (int rc = pull_link_params(s)) return rc;
+    const size_t stride = static_cast<size_t>(s->wpar_stride);
+    std::vector<float> keep(10 * (static_cast<size_t>(s->n) + 1));
+    for (int32_t w = 0; w < s->W; ++w) {
+        float* rec = s->h_wpar.data() + w * stride;
+        for (int l = -1; l < s->n; ++l) std::memcpy(keep.data() + 10 * (l + 1), link_words(rec, l), 10 * sizeof(float));
+        fill_link_record(s, rec);
+        for (int l = -1; l < s->n; ++l) std::memcpy(link_words(rec, l), keep.data() + 10 * (l + 1), 10 * sizeof(float));
+    }
+    return upload_link_params(s, 0, s->W);
+}
 
 // host mirror -> device, worlds [w0, w0 + nw)
 int upload_ground_friction(mw_sim* s, int32_t w0, int32_t nw) {
@@ -320,7 +398,7 @@ int upload_params(mw_sim* s) {
         build_float(s);
         MW_HIP(hipMemcpyAsync(s->d_params.get(), &s->h_params, sizeof(mw::ChainF), hipMemcpyHostToDevice, s->stream));
         MW_HIP(hipMemcpyAsync(s->d_float.get(), &s->h_float, sizeof(mw::FloatF), hipMemcpyHostToDevice, s->stream));
-        return MW_OK;
+        return refresh_link_params(s);  // the per-world copies of the body block follow the shared one
     }
     if (s->floating) {
         build_free(s);
@@ -995,6 +1073,8 @@ int run_impl(mw_sim* s, int paused, bool readback) {
     if (a.lcp_solves > 0) a.pgs_tol = std::max(a.pgs_tol, kExactPgsTol);
     a.first = 1;
     a.mu = s->wave ? s->d_mu.get() : nullptr;
+    a.wpar = s->wave ? s->d_wpar.get() : nullptr;
+    a.wpar_stride = s->wpar_stride;
     const int spr = s->cfg.steps_per_run;
     int done = 0;
     do {
@@ -1763,6 +1843,56 @@ int mw_ground_friction(mw_sim* s, int32_t w0, int32_t nw, double* mu) {
         if (int rc = pull_ground_friction(s)) return rc;
     }
     for (int32_t k = 0; k < nw; ++k) mu[k] = s->d_mu ? s->h_mu[w0 + k] : static_cast<float>(s->ground_mu);
+    return MW_OK;
+}
+
+// Per-world inertial words of one link (wave kernel): the float32 words the
+// run kernel reads from mw_sim::d_wpar, from the next run on.
+static int check_link_params(const mw_sim* s, int32_t w0, int32_t nw, int32_t link, const void* params) {
+    if (!s || !s->loaded) return fail(MW_ESTATE, "no model loaded");
+    if (!s->initialized) return fail(MW_ESTATE, "the simulator is not initialized");
+    if (!s->wave)
+        return fail(MW_ESTATE, "per-world link parameters need the world-per-wavefront kernel (articulated floating "
+                               "bases, mw_float_kernel == 2; generic fixed-base trees)");
+    if (!params && nw > 0) return fail(MW_EINVAL, "null argument");
+    if (w0 < 0 || nw < 0 || w0 + nw > s->W) return fail(MW_EINVAL, "world range out of bounds");
+    if (link < -1 || link >= s->n)
+        return fail(MW_EINVAL, "link " + std::to_string(link) + " out of range [-1, " + std::to_string(s->n) + ")");
+    return MW_OK;
+}
+
+int mw_set_link_params(mw_sim* s, int32_t w0, int32_t nw, int32_t link, const float* params) {
+    if (int rc = check_link_params(s, w0, nw, link, params)) return rc;
+    if (s->env_inertia)
+        return fail(MW_ESTATE, "mw_set_link_params: a floating-base env with inertia randomisation owns this "
+                               "simulator's per-world link parameters (they live on the device); destroy the env "
+                               "first");
+    for (int32_t k = 0; k < nw; ++k) {
+        const float* p = params + 10 * static_cast<size_t>(k);
+        for (int e = 0; e < 10; ++e)
+            if (!std::isfinite(p[e])) return fail(MW_EINVAL, "the link parameters must be finite");
+        if (!(p[0] > 0.f)) return fail(MW_EINVAL, "the link mass must be > 0");
+    }
+    MW_HIP(hipSetDevice(s->cfg.device));
+    if (int rc = alloc_link_params(s)) return rc;
+    for (int32_t k = 0; k < nw; ++k)
+        std::memcpy(link_words(s->h_wpar.data() + static_cast<size_t>(w0 + k) * s->wpar_stride, link),
+                    params + 10 * static_cast<size_t>(k), 10 * sizeof(float));
+    return upload_link_params(s, w0, nw);
+}
+
+int mw_link_params(mw_sim* s, int32_t w0, int32_t nw, int32_t link, float* params) {
+    if (int rc = check_link_params(s, w0, nw, link, params)) return rc;
+    if (s->env_inertia) {  // the env's kernels write the records
+        MW_HIP(hipSetDevice(s->cfg.device));
+        if (int rc = pull_link_params(s)) return rc;
+    }
+    const float* nominal = link < 0 ? &s->h_float.mass : &s->h_params.b[link].mass;
+    for (int32_t k = 0; k < nw; ++k)
+        std::memcpy(params + 10 * static_cast<size_t>(k),
+                    s->d_wpar ? link_words(s->h_wpar.data() + static_cast<size_t>(w0 + k) * s->wpar_stride, link)
+                              : nominal,
+                    10 * sizeof(float));
     return MW_OK;
 }
 

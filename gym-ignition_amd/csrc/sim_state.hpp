@@ -133,6 +133,17 @@ struct mw_sim {
     // an env with friction randomisation writes d_mu on the device: the host
     // setters fail with MW_ESTATE, mw_ground_friction reads the device copy
     bool env_friction = false;
+    // per-world link parameters (mw_set_link_params, wave kernel): W records of
+    // wpar_stride words on the device (RunArgs::wpar, kernels.hpp) and their
+    // host mirror; allocated by the first call, together with d_mu (the
+    // kernel's per-world-parameter instances read the friction per world too)
+    mw::dev_ptr<float[]> d_wpar;
+    std::vector<float> h_wpar;
+    int wpar_stride = 0;
+    // an env with inertia randomisation (mw_floatenv_inertia) writes d_wpar on
+    // the device: mw_set_link_params fails with MW_ESTATE, mw_link_params reads
+    // the device copy
+    bool env_inertia = false;
     mw::pin_ptr<int[]> h_overflow;  // pinned copy read back with each synchronous run
     int64_t overflow_seen = 0;    // drops already reported
     // divergence detection: [W] sticky per-world flags + the uint64 count of
@@ -180,3 +191,7 @@ mw::PidSet pid_set(const mw_sim* s);
 int alloc_env_wrench(mw_sim* s);
 int alloc_ground_friction(mw_sim* s);
 int pull_ground_friction(mw_sim* s);  // device copy -> host mirror (synchronises)
+// the per-world link parameter records, every world at the model's nominal
+// words (and the friction array with them); device copy -> host mirror
+int alloc_link_params(mw_sim* s);
+int pull_link_params(mw_sim* s);

@@ -348,6 +348,51 @@ int mw_floatenv_locomotion(mw_vecenv* e, const mw_float_loco_config* cfg, float*
     return MW_OK;
 }
 
+// Inertia randomisation of a floating-base env: the post launch (and the
+// reset's) draws the link masses and the base payload of every episode it
+// starts into the simulator's per-world link parameters, which the run reads
+// (the INERT instances of float_env_kernel.hip).
+int mw_floatenv_inertia(mw_vecenv* e, const mw_float_inertia_config* cfg, float* inertial_out, float* draw_out) {
+    if (!e || !cfg) return fail(MW_EINVAL, "null argument");
+    if (!e->floatenv) return fail(MW_ESTATE, "mw_floatenv_inertia needs an env made by mw_floatenv_create");
+    if (e->was_reset) return fail(MW_ESTATE, "mw_floatenv_inertia must be called before the first mw_vecenv_reset");
+    const float fields[] = {cfg->mass_scale_lo, cfg->mass_scale_hi, cfg->payload_lo, cfg->payload_hi,
+                            cfg->payload_box[0], cfg->payload_box[1], cfg->payload_box[2]};
+    for (float f : fields)
+        if (!std::isfinite(f)) return fail(MW_EINVAL, "every field of mw_float_inertia_config must be finite");
+    const bool scale = cfg->mass_scale_hi > 0.f, payload = cfg->payload_hi > 0.f;
+    if (scale ? !(cfg->mass_scale_lo > 0.f && cfg->mass_scale_lo <= cfg->mass_scale_hi)
+              : (cfg->mass_scale_lo != 0.f || cfg->mass_scale_hi < 0.f))
+        return fail(MW_EINVAL, "the mass scale range needs 0 < mass_scale_lo <= mass_scale_hi (or both 0: off)");
+    if (!(cfg->payload_lo >= 0.f) || !(cfg->payload_hi >= cfg->payload_lo))
+        return fail(MW_EINVAL, "the payload range needs 0 <= payload_lo <= payload_hi");
+    for (int k = 0; k < 3; ++k)
+        if (!(cfg->payload_box[k] >= 0.f)) return fail(MW_EINVAL, "payload_box must be >= 0");
+    mw_sim* s = e->sim;
+    mw::FloatInertiaF& I = e->ftask.inertia;
+    if (!scale && !payload) {  // everything off: the env as it was made
+        if (I.wpar) s->env_inertia = false;
+        I = mw::FloatInertiaF{};
+        return MW_OK;
+    }
+    MW_HIP(hipSetDevice(s->cfg.device));
+    // the allocation first: a failed call leaves the env as it was
+    if (int rc = alloc_link_params(s)) return rc;
+    I = mw::FloatInertiaF{};
+    I.mass_lo = scale ? cfg->mass_scale_lo : 0.f;
+    I.mass_hi = scale ? cfg->mass_scale_hi : 0.f;
+    I.payload_lo = payload ? cfg->payload_lo : 0.f;
+    I.payload_hi = payload ? cfg->payload_hi : 0.f;
+    for (int k = 0; k < 3; ++k) I.payload_box[k] = cfg->payload_box[k];
+    I.stride = s->wpar_stride;
+    std::memcpy(I.base0, &s->h_float.mass, sizeof(I.base0));
+    I.wpar = s->d_wpar.get();
+    I.inertial_out = inertial_out;
+    I.draw_out = draw_out;
+    s->env_inertia = true;
+    return MW_OK;
+}
+
 static int floatenv_reset(mw_vecenv* e, float* obs) {
     mw_sim* s = e->sim;
     e->was_reset = true;
@@ -385,6 +430,12 @@ void mw_vecenv_destroy(mw_vecenv* e) {
             (void)hipSetDevice(s->cfg.device);
             (void)pull_ground_friction(s);
             s->env_friction = false;
+        }
+        if (s->env_inertia) {
+            // ... and the last episode's link parameters
+            (void)hipSetDevice(s->cfg.device);
+            (void)pull_link_params(s);
+            s->env_inertia = false;
         }
     }
     delete e;

@@ -225,11 +225,14 @@ namespace dev {
 // serial inward pass), so the sums are deterministic.  Every lane then has
 // IA0 and B0 of the base (broadcast reads) and solves a0 itself.  Returns a0
 // and leaves qdd_i in qdd_out (L.qdd, LDS) and the per-body records that the
-// later phases read (R, p, U, psi, depth, Rw, pw) in L.body.
+// later phases read (R, p, U, psi, depth, Rw, pw) in L.body.  bw: the base's
+// ten inertial words (mass, com, Io: &F->mass, or the world's own row of
+// RunArgs::wpar); P is then the world's own body block as well.
 template <int MAXN>
 __device__ __forceinline__ SV wave_aba(const ChainF* __restrict__ P, const FloatF* __restrict__ F, int N,
                                        const M3& R0, const f3& p0, const SV& V0, WaveWorld<MAXN>& L, Chol6& L0,
-                                       float dt, float* qdd_out, bool ext, unsigned long long* prof) {
+                                       float dt, float* qdd_out, bool ext, unsigned long long* prof,
+                                       const float* __restrict__ bw) {
     (void)prof;
     MW_PROF_T(ta0);
     const int lane = lane_id();
@@ -365,16 +368,16 @@ __device__ __forceinline__ SV wave_aba(const ChainF* __restrict__ P, const Float
     // and it absorbs every impulse (wave_response), V0 stays 0
     SV a0 = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
     if (!F->fixed) {
-        SI IA0 = rigid_base(*F);
+        SI IA0 = rigid_base(bw);
         IA0 += IA0s;
-        const SV B0 = rigid_bias(F->mass, mk(F->com[0], F->com[1], F->com[2]),
-                                 Sy{F->Io[0], F->Io[1], F->Io[2], F->Io[3], F->Io[4], F->Io[5]}, V0, mulT(R0, gw)) +
+        const SV B0 = rigid_bias(bw[0], mk(bw[1], bw[2], bw[3]), Sy{bw[4], bw[5], bw[6], bw[7], bw[8], bw[9]}, V0,
+                                 mulT(R0, gw)) +
                       B0s;
 
         L0.factor(IA0);
         a0 = L0.solve(-1.f * B0);
         if (dual) {
-            SI IA0n = rigid_base(*F);
+            SI IA0n = rigid_base(bw);
             IA0n += IA0ns;
             L0.factor(IA0n);  // L0 leaves with the impulses' (non-implicit) base inertia
         }
@@ -531,19 +534,20 @@ __device__ __forceinline__ void wave_pgs(const WaveWorld<MAXN>& L, const float (
 
 // One engine step of world L (state in L.q / L.qd / base; joint forces in
 // L.tau).  Returns the active slot mask; *overflow += rows dropped.  mu_w:
-// the world's ground friction coefficient (wave-uniform address).
+// the world's ground friction coefficient (wave-uniform address); bw: the
+// base's ten inertial words (wave_aba).
 template <int MAXN, bool CONS>
 __device__ __forceinline__ uint32_t wave_step(const ChainF* __restrict__ P, const FloatF* __restrict__ F, int N,
                                               FreeState& base, WaveWorld<MAXN>& L, float dt, int pgs_iters,
                                               float pgs_tol, bool warm, int lcp_solves, float* qdd_out, int* overflow,
                                               int* unconverged, unsigned long long* prof, bool ext,
-                                              const float* __restrict__ mu_w) {
+                                              const float* __restrict__ mu_w, const float* __restrict__ bw) {
     const int lane = lane_id();
     const int NV = 6 + N;
     MW_PROF_T(t0);
     const M3 R0 = quat_to_R(base.qw, base.qx, base.qy, base.qz);
     Chol6 L0;  // on return: the factorisation the impulses use
-    const SV a0 = wave_aba<MAXN>(P, F, N, R0, base.p, base.V, L, L0, dt, qdd_out, ext, prof);
+    const SV a0 = wave_aba<MAXN>(P, F, N, R0, base.p, base.V, L, L0, dt, qdd_out, ext, prof, bw);
     MW_PROF_T(t1);
     MW_PROF_ACC(1, t0, t1);
     // integrateVelocities (lane e: nu component e)

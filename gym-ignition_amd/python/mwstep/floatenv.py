@@ -22,7 +22,9 @@ resets: the host setters of ``env.sim`` that write them (``set("force_target"
 With pushes on it also owns the simulator's wrench buffer
 (``apply_world_wrench`` raises), with friction randomisation on the per-world
 ground friction (``set_ground_friction`` / ``set_ground_plane`` raise,
-``ground_friction()`` reads the device copy).
+``ground_friction()`` reads the device copy), with inertia randomisation on
+the per-world link parameters (``set_link_params`` raises, ``link_params()``
+reads the device copy).
 
 ``task="locomotion"`` (``mw_floatenv_locomotion``) turns the env into a
 velocity-command task, still three launches per step: every world follows a
@@ -84,6 +86,9 @@ class FloatVecEnv:
                  device: int = 0, pgs_iters: int = 20, ground_mu: float = 1.0,
                  push_interval: int = 0, push_steps: int = 1, push_force: float = 0.0, push_torque: float = 0.0,
                  friction_range: Optional[Sequence[float]] = None,
+                 mass_scale_range: Optional[Sequence[float]] = None,
+                 payload_range: Optional[Sequence[float]] = None,
+                 payload_box: Sequence[float] = (0.0, 0.0, 0.0),
                  task: str = "forward",
                  command_ranges: Sequence[Sequence[float]] = ((0.0, 0.0), (0.0, 0.0), (0.0, 0.0)),
                  cmd_interval: int = 0, cmd_zero_prob: float = 0.0, cmd_min: float = 0.0,
@@ -109,6 +114,18 @@ class FloatVecEnv:
         ``env.push`` ``[n_worlds, 6]`` holds the wrench the last step applied and
         ``env.friction`` ``[n_worlds]`` the current coefficients; both are also
         in ``info`` (``"push"``, ``"friction"``) when the feature is on.
+
+        Inertia randomisation (``mw_floatenv_inertia``), drawn anew at each
+        reset: ``mass_scale_range`` ``(lo, hi)`` scales the mass and the
+        rotational inertia of every link, the base included, by its own factor
+        U(lo, hi); ``payload_range`` ``(lo, hi)`` kg adds a point mass to the
+        base at a position uniform in ±``payload_box`` (m, base frame).
+        ``env.inertial`` ``[n_worlds, n + 1, 10]`` (also ``info["inertial"]``)
+        holds the words in force for the current episode, base first, in the
+        layout of ``Simulator.set_link_params``, and ``env.inertia_draws``
+        ``[n_worlds, n + 5]`` (``info["inertia_draws"]``) the draws themselves:
+        the ``n + 1`` scales, the payload mass and its position; both ``None``
+        with the feature off.
 
         ``task="locomotion"``: ``command_ranges`` holds the ``(lo, hi)`` of
         v_x, v_y (m/s) and the yaw rate (rad/s); a command is drawn every
@@ -224,6 +241,23 @@ class FloatVecEnv:
             N.check(N.lib().mw_floatenv_randomize(
                 h, ctypes.byref(rc), None if self.push is None else ctypes.c_void_p(self.push.data_ptr()),
                 None if self.friction is None else ctypes.c_void_p(self.friction.data_ptr())), "mw_floatenv_randomize")
+
+        self.inertial = self.inertia_draws = None
+        if mass_scale_range is not None or payload_range is not None:
+            slo, shi = (0.0, 0.0) if mass_scale_range is None else mass_scale_range
+            plo, phi = (0.0, 0.0) if payload_range is None else payload_range
+            if len(payload_box) != 3:
+                raise ValueError("payload_box must hold three half extents (m)")
+            if shi > 0 or phi > 0:
+                nominal = np.stack([sim.link_params(k - 1, [0])[0] for k in range(n + 1)])
+                self.inertial = self._info["inertial"] = torch.from_numpy(
+                    np.ascontiguousarray(np.broadcast_to(nominal, (n_worlds, n + 1, 10)))).to(self.device)
+                self.inertia_draws = self._info["inertia_draws"] = torch.zeros((n_worlds, n + 5), **f32)
+                self.inertia_draws[:, :n + 1] = 1.0
+            ic = N.MwFloatInertiaConfig(slo, shi, plo, phi, (ctypes.c_float * 3)(*[float(b) for b in payload_box]))
+            ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+            N.check(N.lib().mw_floatenv_inertia(h, ctypes.byref(ic), ptr(self.inertial), ptr(self.inertia_draws)),
+                    "mw_floatenv_inertia")
 
     # ------------------------------------------------------------------
     # what quadruped() / icub() add for task="locomotion" unless the caller sets it

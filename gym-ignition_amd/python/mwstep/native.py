@@ -127,6 +127,17 @@ class MwFloatLocoConfig(ctypes.Structure):
     ]
 
 
+class MwFloatInertiaConfig(ctypes.Structure):
+    """mw_float_inertia_config (include/mwstep.h)."""
+    _fields_ = [
+        ("mass_scale_lo", ctypes.c_float),
+        ("mass_scale_hi", ctypes.c_float),
+        ("payload_lo", ctypes.c_float),
+        ("payload_hi", ctypes.c_float),
+        ("payload_box", ctypes.c_float * 3),
+    ]
+
+
 # (name, restype, argtypes) of every symbol in include/mwstep.h
 _P = ctypes.c_void_p
 _I = ctypes.c_int32
@@ -196,6 +207,8 @@ SIGNATURES = [
     ("mw_set_ground_plane", ctypes.c_int, [_P, _I, ctypes.c_double]),
     ("mw_set_ground_friction", ctypes.c_int, [_P, _I, _I, _D]),
     ("mw_ground_friction", ctypes.c_int, [_P, _I, _I, _D]),
+    ("mw_set_link_params", ctypes.c_int, [_P, _I, _I, _I, ctypes.POINTER(ctypes.c_float)]),
+    ("mw_link_params", ctypes.c_int, [_P, _I, _I, _I, ctypes.POINTER(ctypes.c_float)]),
     ("mw_enable_contacts", ctypes.c_int, [_P, _I]),
     ("mw_contacts_enabled", ctypes.c_int, [_P, _IP]),
     ("mw_get_contacts", ctypes.c_int, [_P, _I, _D, _I, _IP]),
@@ -220,6 +233,7 @@ SIGNATURES = [
     ("mw_floatenv_create", ctypes.c_int, [_P, ctypes.POINTER(MwFloatTaskConfig), ctypes.POINTER(_P)]),
     ("mw_floatenv_randomize", ctypes.c_int, [_P, ctypes.POINTER(MwFloatRandConfig), _P, _P]),
     ("mw_floatenv_locomotion", ctypes.c_int, [_P, ctypes.POINTER(MwFloatLocoConfig), _P]),
+    ("mw_floatenv_inertia", ctypes.c_int, [_P, ctypes.POINTER(MwFloatInertiaConfig), _P, _P]),
 ]
 
 # include/mwscene.h

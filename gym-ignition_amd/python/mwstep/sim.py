@@ -270,6 +270,86 @@ class Simulator:
         N.check(N.lib().mw_ground_friction(self.handle, int(w0), int(nw), N.dptr(out)), "ground_friction")
         return out
 
+    # -- per-world link parameters (mwstep.h: mw_set_link_params)
+    def link_index(self, link) -> int:
+        """-1 for the base link (or its name), the dof index for the link a
+        joint moves (or its name)."""
+        if isinstance(link, str):
+            if link == self.base_frame:
+                return -1
+            try:
+                return self.link_names.index(link)
+            except ValueError:
+                raise ValueError(f"link {link!r} not found in model {self.model_name!r} (links welded by fixed "
+                                 f"joints are part of their parent's body)") from None
+        return int(link)
+
+    def _worlds(self, worlds):
+        """None = every world; a slice-like (w0, nw) or a range stays one call."""
+        if worlds is None:
+            return [(0, self.n_worlds)]
+        ws = np.asarray(list(worlds) if not np.isscalar(worlds) else [worlds], dtype=np.int64)
+        if len(ws) and np.array_equal(ws, np.arange(ws[0], ws[0] + len(ws))):
+            return [(int(ws[0]), len(ws))]
+        return [(int(w), 1) for w in ws]
+
+    def set_link_params(self, link, params, worlds=None) -> None:
+        """mw_set_link_params: the inertial words of ``link`` (name or index,
+        -1 = the base) per world, ``[k, 10]`` or ``[10]`` for all ``k`` worlds
+        of ``worlds`` (``None`` = every world): mass, centre of mass xyz (link
+        frame), rotational inertia about the link *origin* xx yy zz xy xz yz.
+        The float32 words are what the kernel reads, from the next run on."""
+        self._cache.clear()
+        li = self.link_index(link)
+        spans = self._worlds(worlds)
+        total = sum(nw for _, nw in spans)
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(params, dtype=np.float32), (total, 10)))
+        fp = ctypes.POINTER(ctypes.c_float)
+        k = 0
+        for w0, nw in spans:
+            N.check(N.lib().mw_set_link_params(self.handle, w0, nw, li, v[k:k + nw].ctypes.data_as(fp)),
+                    "set_link_params")
+            k += nw
+
+    def link_params(self, link, worlds=None) -> np.ndarray:
+        """float32 ``[k, 10]``: the words the next run will use (the model's
+        nominal ones until ``set_link_params`` or an env's draw changed them)."""
+        li = self.link_index(link)
+        spans = self._worlds(worlds)
+        out = np.zeros((sum(nw for _, nw in spans), 10), dtype=np.float32)
+        fp = ctypes.POINTER(ctypes.c_float)
+        k = 0
+        for w0, nw in spans:
+            N.check(N.lib().mw_link_params(self.handle, w0, nw, li, out[k:k + nw].ctypes.data_as(fp)), "link_params")
+            k += nw
+        return out
+
+    @staticmethod
+    def inertial_words(mass, com, inertia_about_com) -> np.ndarray:
+        """The ten float32 words of a link from its mass, centre of mass and
+        rotational inertia about the centre of mass (3x3, or xx yy zz xy xz
+        yz): the parallel-axis shift to the link origin in fp64, rounded once.
+        Leading dimensions broadcast."""
+        m = np.asarray(mass, dtype=np.float64)[..., None]
+        c = np.asarray(com, dtype=np.float64)
+        ic = np.asarray(inertia_about_com, dtype=np.float64)
+        if ic.shape[-2:] == (3, 3):
+            ic = np.stack([ic[..., 0, 0], ic[..., 1, 1], ic[..., 2, 2], ic[..., 0, 1], ic[..., 0, 2], ic[..., 1, 2]], -1)
+        c2 = (c * c).sum(-1, keepdims=True)
+        shift = np.concatenate([c2 - c * c, -c[..., [0]] * c[..., [1]], -c[..., [0]] * c[..., [2]],
+                                -c[..., [1]] * c[..., [2]]], -1)
+        shape = np.broadcast_shapes(m.shape[:-1], c.shape[:-1], ic.shape[:-1])
+        out = np.empty(shape + (10,))
+        out[..., 0:1] = m
+        out[..., 1:4] = c
+        out[..., 4:10] = ic + m * shift
+        return out.astype(np.float32)
+
+    def set_link_inertial(self, link, mass, com, inertia_about_com, worlds=None) -> None:
+        """``set_link_params`` from the mass, the centre of mass and the
+        inertia about the centre of mass (``inertial_words``)."""
+        self.set_link_params(link, self.inertial_words(mass, com, inertia_about_com), worlds)
+
     def enable_contacts(self, enable: bool = True) -> None:
         self._cache.clear()
         N.check(N.lib().mw_enable_contacts(self.handle, 1 if enable else 0))

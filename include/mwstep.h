@@ -287,6 +287,28 @@ int mw_set_ground_plane(mw_sim* sim, int32_t enabled, double mu);
  * not hold it. */
 int mw_set_ground_friction(mw_sim* sim, int32_t w0, int32_t nw, const double* mu);
 int mw_ground_friction(mw_sim* sim, int32_t w0, int32_t nw, double* mu);
+/* Per-world inertial parameters of one link, worlds [w0, w0 + nw):
+ * params[nw][10] are the kernel's own float32 words, set and read back bit for
+ * bit -- mass (> 0), centre of mass xyz in the link frame, rotational inertia
+ * about the link ORIGIN (not the centre of mass) as xx yy zz xy xz yz; all
+ * finite, else MW_EINVAL.  link -1 = the base, i = the body of dof i (the
+ * numbering of mw_get_contact_bodies and mw_apply_link_wrench); links welded
+ * by fixed joints are part of their body.  Used from the next run on.  Models
+ * stepped by the world-per-wavefront kernel only (mw_float_kernel == 2,
+ * generic fixed-base trees); others fail with MW_ESTATE.  The storage (one
+ * copy of the model's body block and the base's words per world) is allocated
+ * by the first mw_set_link_params; until then, and for every world and link
+ * never set, mw_link_params returns the model's nominal words.  While a
+ * floating-base env randomises the inertias (mw_floatenv_inertia)
+ * mw_set_link_params fails with MW_ESTATE and mw_link_params reads the env's
+ * device copy back.  These are parameters, not state: mw_get_state /
+ * mw_set_state records do not hold them.  Quantities the host derives from
+ * the model (mw_device_params / mw_device_float_params, the choice of the
+ * kernel's instance) keep the nominal model.  Setters of the shared model
+ * (mw_set_joint_param, mw_set_gravity) reach every world's copy and leave its
+ * inertial words as they are. */
+int mw_set_link_params(mw_sim* sim, int32_t w0, int32_t nw, int32_t link, const float* params);
+int mw_link_params(mw_sim* sim, int32_t w0, int32_t nw, int32_t link, float* params);
 /* Model::enableContacts / contactsEnabled (Model.cpp:674-700). */
 int mw_enable_contacts(mw_sim* sim, int32_t enable);
 int mw_contacts_enabled(const mw_sim* sim, int32_t* enabled);
@@ -570,6 +592,43 @@ typedef struct {
     float contact_force_min;        /* N                                          */
 } mw_float_loco_config;
 int mw_floatenv_locomotion(mw_vecenv* env, const mw_float_loco_config* cfg, float* command_dev);
+
+/* Inertia randomisation of a floating-base env: per-world link masses and a
+ * payload on the base, drawn on the device wherever a reset is issued (every
+ * world on mw_vecenv_reset).  Call it after mw_floatenv_create and before the
+ * first mw_vecenv_reset (MW_ESTATE after it, or on another kind of env), in
+ * any order with mw_floatenv_randomize and mw_floatenv_locomotion.  The step
+ * stays three launches without host copies or synchronisation; a refused call
+ * leaves the env as it was.  The draws are words of new blocks of the Philox
+ * counter (global world, episode, block, 0) mw_floatenv_randomize describes,
+ * so they are a pure function of (seed, global world, episode):
+ *   scales   link k (0 = the base, 1 + i = the body of dof i) takes s_k =
+ *            U(mass_scale_lo, mass_scale_hi) from word k % 4 of block
+ *            0x40000100 | (k / 4): mass = s mass0, Io[j] = s Io0[j], the centre
+ *            of mass kept (mass0, Io0: the model's nominal float32 words).  On
+ *            when mass_scale_hi > 0; needs 0 < lo <= hi.
+ *   payload  a point mass m_p = U(payload_lo, payload_hi) kg at p =
+ *            (U(-box_x, box_x), U(-box_y, box_y), U(-box_z, box_z)) m in the
+ *            base frame, words 0..3 of block 0x40000180, added to the (scaled)
+ *            base:  m' = m + m_p,  com' = (m com + m_p p) / m',
+ *            Io' = Io + m_p (|p|^2 1 - p p^T).  On when payload_hi > 0; needs
+ *            0 <= lo <= hi and payload_box >= 0.
+ * A feature that is off is skipped, not fed neutral values.  The words are
+ * written into the simulator's per-world link parameters (mw_link_params
+ * reads them back) and the run that applies the reset reads them with it.
+ * inertial_dev float32 [n_worlds, n_dofs + 1, 10] is a caller-owned device
+ * buffer (may be NULL) that must outlive the env: every reset writes the words
+ * in force for the new episode, base first, in mw_set_link_params' layout.
+ * draws_dev float32 [n_worlds, n_dofs + 5], likewise: the draws themselves,
+ * s_0 .. s_n, m_p, p xyz (scales of 1 and a zero payload where a feature is
+ * off) -- what a critic with privileged information would be given.
+ * While such an env exists mw_set_link_params fails with MW_ESTATE. */
+typedef struct {
+    float mass_scale_lo, mass_scale_hi; /* 0 < lo <= hi; hi > 0 turns it on  */
+    float payload_lo, payload_hi;       /* kg, 0 <= lo <= hi; hi > 0 turns it on */
+    float payload_box[3];               /* m, half extents in the base frame */
+} mw_float_inertia_config;
+int mw_floatenv_inertia(mw_vecenv* env, const mw_float_inertia_config* cfg, float* inertial_dev, float* draws_dev);
 
 #ifdef __cplusplus
 }

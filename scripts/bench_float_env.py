@@ -28,6 +28,16 @@ of both env kernels, 12 + n more observation words and the kept action row
 per world), fed zero actions -- the home posture through action_scale, the
 same physics as env -- and reports env_loco - env.
 
+--inertia adds two envs with the inertia randomisation on
+(mw_floatenv_inertia: the WPAR instances of the run kernel, which read every
+world's own body block and base words, and the INERT instance of the post
+kernel): env_wpar with mass_scale_range (1, 1), whose per-world records hold
+the nominal words -- the same physics as env, so env_wpar - env is the cost of
+the mechanism: distinct parameter lines per wave instead of one shared block
+-- and env_inertia with real ranges, whose difference from env_wpar is the cost
+of the dynamics of robots that differ.  No world resets inside the timed
+windows (max_episode_steps 0), so the draw itself runs at reset() only.
+
 Not a bench.py leg.  Prints one JSON line per model."""
 
 import argparse
@@ -42,6 +52,8 @@ RANDOMIZE = dict(push_interval=50, push_steps=5, push_force=30.0, push_torque=5.
 # --task locomotion: commands redrawn every 100 steps, every reward term on
 LOCOMOTION = dict(task="locomotion", command_ranges=((-1.0, 1.0), (-0.5, 0.5), (-1.0, 1.0)), cmd_interval=100,
                   cmd_zero_prob=0.1, cmd_min=0.1, w_lin_z=2.0, w_ang_xy=0.05, w_action_rate=0.01, w_air_time=1.0)
+# --inertia: every link's mass within -20 % / +25 %, up to 5 kg on the base
+INERTIA = dict(mass_scale_range=(0.8, 1.25), payload_range=(0.0, 5.0), payload_box=(0.1, 0.1, 0.05))
 sys.path.insert(0, os.path.join(ROOT, "gym-ignition_amd", "python"))
 
 
@@ -124,6 +136,15 @@ def measure(torch, args, model, W):
             loco.reset()
             zeros = torch.zeros((W, loco.action_dim), dtype=torch.float32, device=loco.device)
         graphs["env_loco"] = capture(torch, stream, lambda: loco.step_raw(zeros.data_ptr()), args.warmup)
+    wpar = inert = None
+    if args.inertia:
+        with torch.cuda.stream(stream):
+            wpar = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0, mass_scale_range=(1.0, 1.0))
+            wpar.reset()
+            inert = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0, **INERTIA)
+            inert.reset()
+        graphs["env_wpar"] = capture(torch, stream, lambda: wpar.step_raw(actions.data_ptr()), args.warmup)
+        graphs["env_inertia"] = capture(torch, stream, lambda: inert.step_raw(actions.data_ptr()), args.warmup)
     times = {k: [] for k in graphs}
     for _ in range(args.rounds):
         for k, g in graphs.items():
@@ -158,6 +179,22 @@ def measure(torch, args, model, W):
                     "loco_bytes_moved_by_env_kernels": W * (loco.obs_dim + 3 * loco.action_dim + 3) * 4,
                     "loco_base_z_range_after": [round(float(zl.min()), 4), round(float(zl.max()), 4)]})
         loco.close()
+    if inert is not None:
+        n = env.action_dim
+        stride = 4 * (16 + 8 + 40 * n)
+        zi = inert.sim.base_pose()[:, 2]
+        same = bool((wpar.sim.get_state() == env.sim.get_state()).all())
+        out.update({"env_wpar_step_us": round(med["env_wpar"], 3), "env_inertia_step_us": round(med["env_inertia"], 3),
+                    "wpar_minus_env_us": round(med["env_wpar"] - med["env"], 3),
+                    "inertia_minus_wpar_us": round(med["env_inertia"] - med["env_wpar"], 3),
+                    "inertia": INERTIA, "wpar_state_equals_env_state": same,
+                    "link_parameter_bytes_per_world": stride, "friction_bytes_per_world": 4,
+                    "inertial_and_draw_output_bytes_per_world": 4 * (10 * (n + 1) + n + 5),
+                    "base_mass_range": [round(float(inert.inertial[:, 0, 0].min()), 3),
+                                        round(float(inert.inertial[:, 0, 0].max()), 3)],
+                    "inertia_base_z_range_after": [round(float(zi.min()), 4), round(float(zi.max()), 4)]})
+        wpar.close()
+        inert.close()
     env.close()
     sim.close()
     return out
@@ -172,6 +209,9 @@ def main():
     p.add_argument("--quadruped-worlds", type=int, default=4096)
     p.add_argument("--randomize", action="store_true",
                    help="also time an env with pushes and friction randomisation on (env_rand)")
+    p.add_argument("--inertia", action="store_true",
+                   help="also time envs with per-world link parameters: nominal words (env_wpar) and real ranges "
+                        "(env_inertia)")
     p.add_argument("--task", choices=("forward", "locomotion"), default="forward",
                    help="locomotion: also time an env with the velocity-command task on (env_loco)")
     args = p.parse_args()
