@@ -13,7 +13,9 @@
 // the friction of every episode it starts into the simulator's per-world
 // array (T.rand.mu), its INERT instance (mw_floatenv_inertia) the link masses
 // and the base payload into the simulator's per-world link parameters
-// (T.inertia.wpar).  The locomotion task (mw_floatenv_locomotion) is the LOCO
+// (T.inertia.wpar), its JOINT instance (mw_floatenv_joints) the joints'
+// damping, friction and effort limit into the same records.
+// The locomotion task (mw_floatenv_locomotion) is the LOCO
 // instance of both env kernels: the action launch keeps the raw action and the
 // action-rate sum and writes the scaled command, the post launch appends the
 // body-frame block of the observation, draws the velocity commands and adds
@@ -40,6 +42,9 @@ namespace dev {
 constexpr int kEnvTile = 64;      // worlds per block (lane = world)
 constexpr int kEnvThreads = 256;  // 4 waves share the tile's columns / rows
 constexpr int kEnvWaves = kEnvThreads / 64;
+static_assert(kFtBodyDamping * 4 == offsetof(BodyF, damping) && kFtBodyFriction * 4 == offsetof(BodyF, friction) &&
+                  kFtBodyEffort * 4 == offsetof(BodyF, effort),
+              "float_task.hpp restates the joint dynamics words of BodyF");
 static_assert(kFtWparBody0 == kWparBaseWords + kWparHeadWords && kFtBodyWords * 4 == sizeof(BodyF) &&
                   kFtBodyInertial * 4 == offsetof(BodyF, mass),
               "float_task.hpp restates the layout of RunArgs::wpar");
@@ -159,7 +164,16 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_action_kernel(const flo
 // the pending reset.  The blocks of four links go round the
 // waves starting at wave 1, so wave 0's chain takes one only from the 13th
 // link on.
-template <bool RAND, bool PUSH, bool LOCO, bool INERT>
+// JOINT (mw_floatenv_joints, T.joints): a reset also draws the joint dynamics
+// of the episode it starts -- joint d of T.joints.dof_mask takes a, f, s from
+// words 0..2 of block kFtJointBlock | d, damping = damping0 + a, friction =
+// friction0 + f, effort = s effort0 (ft_joint_words; the nominal words from P,
+// the shared ChainF) -- into words 26, 27 and 30 of the joint's BodyF in the
+// same record: one Philox call and three stores per joint.  A feature that is
+// off draws nothing and a joint outside the mask leaves its record alone; both
+// report the nominal words and the draws 0, 0, 1 (T.joints.joints_out,
+// draw_out).  The joints go round the waves starting at wave 1.
+template <bool RAND, bool PUSH, bool LOCO, bool INERT, bool JOINT>
 __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const ChainF* __restrict__ P, FloatTaskF T,
                                                                      SimDev S, FreeDev D, VecDev V,
                                                                      const float* __restrict__ asq,
@@ -414,6 +428,40 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
                 }
             }
         }
+        if constexpr (JOINT) {
+            const FloatJointF& J = T.joints;
+            const uint32_t g = T.world_offset + static_cast<uint32_t>(w);
+            const bool damp = J.damping_hi > 0.f, fric = J.friction_hi > 0.f, eff = J.effort_hi > 0.f;
+            float* __restrict__ rec = J.wpar + static_cast<size_t>(w) * J.stride + kFtWparBody0;
+            float* __restrict__ out = J.joints_out ? J.joints_out + static_cast<size_t>(w) * n * 3 : nullptr;
+            float* __restrict__ draw = J.draw_out ? J.draw_out + static_cast<size_t>(w) * n * 3 : nullptr;
+            for (int d = (wave + kEnvWaves - 1) % kEnvWaves; d < n; d += kEnvWaves) {
+                const BodyF& b0 = P->b[d];
+                const float nom[3] = {b0.damping, b0.friction, b0.effort};
+                float a[3] = {0.f, 0.f, 1.f}, wd[3] = {nom[0], nom[1], nom[2]};
+                if ((J.dof_mask >> d) & 1u) {
+                    uint32_t r[4];
+                    philox(T.seed_lo, T.seed_hi, g, episode, r, ft_joint_block(d));
+                    if (damp) a[0] = unif(r[0], J.damping_lo, J.damping_hi);
+                    if (fric) a[1] = unif(r[1], J.friction_lo, J.friction_hi);
+                    if (eff) a[2] = unif(r[2], J.effort_lo, J.effort_hi);
+                    float wn[3];
+                    ft_joint_words(nom, a, wn);
+                    if (damp) wd[0] = wn[0];
+                    if (fric) wd[1] = wn[1];
+                    if (eff) wd[2] = wn[2];
+                    float* __restrict__ dst = rec + d * kFtBodyWords;
+                    dst[kFtBodyDamping] = wd[0];
+                    dst[kFtBodyFriction] = wd[1];
+                    dst[kFtBodyEffort] = wd[2];
+                }
+#pragma unroll
+                for (int e = 0; e < 3; ++e) {
+                    if (out) out[d * 3 + e] = wd[e];
+                    if (draw) draw[d * 3 + e] = a[e];
+                }
+            }
+        }
         for (int j = wave; j < T.n_links; j += kEnvWaves) {
             row[13 + 2 * n + j] = 0.f;
             if constexpr (LOCO) T.loco.air_steps[j * Ws + w] = 0u;
@@ -478,24 +526,31 @@ hipError_t launch_float_env_post(const ChainF* P, const FloatTaskF& T, const Sim
     // links) 64 x 177 words = 45 KB, with the kernel's 3.3 KB of static LDS
     // still inside the 64 KB a block gets without asking for more.
     const bool rand = T.rand.friction_hi > 0.f, push = T.rand.push_interval > 0u, loco = T.loco.on != 0u;
-    const bool inert = T.inertia.wpar != nullptr;
-#define MW_POST(R_, P_, L_, I_)                                                                                     \
-    hipLaunchKernelGGL((dev::float_env_post_kernel<R_, P_, L_, I_>), grid, block, lds, st, P, T, S, D, V, asq, obs, \
+    const bool inert = T.inertia.wpar != nullptr, joint = T.joints.wpar != nullptr;
+#define MW_POST(R_, P_, L_, I_, J_)                                                                                  \
+    hipLaunchKernelGGL((dev::float_env_post_kernel<R_, P_, L_, I_, J_>), grid, block, lds, st, P, T, S, D, V, asq, obs, \
                        reward, done, term_obs, n, W, reset_all)
-#define MW_POST_RP(L_, I_)                           \
-    if (rand && push) MW_POST(true, true, L_, I_);   \
-    else if (rand) MW_POST(true, false, L_, I_);     \
-    else if (push) MW_POST(false, true, L_, I_);     \
-    else MW_POST(false, false, L_, I_)
-    if (loco && inert) {
-        MW_POST_RP(true, true);
-    } else if (loco) {
-        MW_POST_RP(true, false);
-    } else if (inert) {
-        MW_POST_RP(false, true);
-    } else {
-        MW_POST_RP(false, false);
+#define MW_POST_RP(L_, I_, J_)                           \
+    if (rand && push) MW_POST(true, true, L_, I_, J_);   \
+    else if (rand) MW_POST(true, false, L_, I_, J_);     \
+    else if (push) MW_POST(false, true, L_, I_, J_);     \
+    else MW_POST(false, false, L_, I_, J_)
+#define MW_POST_LI(J_)                 \
+    if (loco && inert) {               \
+        MW_POST_RP(true, true, J_);    \
+    } else if (loco) {                 \
+        MW_POST_RP(true, false, J_);   \
+    } else if (inert) {                \
+        MW_POST_RP(false, true, J_);   \
+    } else {                           \
+        MW_POST_RP(false, false, J_);  \
     }
+    if (joint) {
+        MW_POST_LI(true)
+    } else {
+        MW_POST_LI(false)
+    }
+#undef MW_POST_LI
 #undef MW_POST_RP
 #undef MW_POST
     return hipGetLastError();

@@ -7,7 +7,9 @@
 // integer arithmetic of the push schedule (mw_floatenv_randomize) is here too,
 // built by tests/host_float_rand/harness.cpp, the inertial words of the
 // inertia randomisation (mw_floatenv_inertia: mass scale, payload), built by
-// tests/host_float_inertia/harness.cpp, and so is the arithmetic of the
+// tests/host_float_inertia/harness.cpp, the joint words of the joint
+// randomisation (mw_floatenv_joints: damping, friction, effort), built by
+// tests/host_float_joints/harness.cpp, and so is the arithmetic of the
 // locomotion task (mw_floatenv_locomotion: commands, projected gravity, the
 // air-time counter, the extra reward terms), built by
 // tests/host_float_loco/harness.cpp.
@@ -90,6 +92,23 @@ constexpr int kFtBodyWords = 40, kFtBodyInertial = 16;  // BodyF words; its ten 
 constexpr uint32_t kFtScaleBlock = 0x40000100u;    // | k / 4, word k % 4: scale of link k (0 = the base), k <= 48
 constexpr uint32_t kFtPayloadBlock = 0x40000180u;  // r[0]: payload mass, r[1..3]: its position
 
+// Joint randomisation of the floating-base env (mw_floatenv_joints): viscous
+// damping and Coulomb friction added to the nominal words, the effort limit
+// scaled, each off when its `hi` is zero; off altogether when wpar is null.
+struct FloatJointF {
+    float damping_lo, damping_hi;    // a ~ U(lo, hi) N m s/rad per joint and episode; on when hi > 0
+    float friction_lo, friction_hi;  // f ~ U(lo, hi) N m; on when hi > 0
+    float effort_lo, effort_hi;      // s ~ U(lo, hi), a factor; on when hi > 0
+    uint64_t dof_mask;               // bit d: joint d is drawn (never 0 here: mw_floatenv_joints fills it)
+    int32_t stride;                  // words between two worlds' records in wpar
+    float* wpar;                     // the simulator's per-world link parameters (mw_sim::d_wpar, RunArgs::wpar)
+    float* joints_out;               // [W, n, 3] damping, friction, effort of the current episode (caller's, may be null)
+    float* draw_out;                 // [W, n, 3] the episode's draws a, f, s (caller's, may be null)
+};
+constexpr int kFtBodyDamping = 26, kFtBodyFriction = 27, kFtBodyEffort = 30;  // BodyF words
+constexpr uint32_t kFtJointBlock = 0x40000200u;  // | d, words 0..2: damping, friction, effort draw of joint d < 48
+constexpr float kFtUnbounded = 3.402823466e+38f;  // FLT_MAX: to_f32 of an infinite effort limit
+
 // Task description of the floating-base env (kernel argument, by value).
 struct FloatTaskF {
     int32_t action_mode;     // 0 torque (SimDev::cmd), 1 position (SimDev::ptgt)
@@ -107,6 +126,7 @@ struct FloatTaskF {
     FloatRandF rand;
     FloatLocoF loco;
     FloatInertiaF inertia;
+    FloatJointF joints;
 };
 
 namespace dev {
@@ -229,6 +249,21 @@ __device__ __forceinline__ void ft_inertia_payload(float (&w)[10], float mp, con
     w[8] = fmaf(-mp, xz, w[8]);
     w[9] = fmaf(-mp, yz, w[9]);
 }
+
+// ---- joint randomisation (FloatJointF) ----
+// nom: the joint's nominal damping, friction and effort words; draw: a, f, s.
+// damping = damping0 + a, friction = friction0 + f, effort = s effort0 with an
+// unbounded limit (kFtUnbounded) kept: one rounding per word, none fused.
+__device__ __forceinline__ void ft_joint_words(const float (&nom)[3], const float (&draw)[3], float (&w)[3]) {
+    MW_FT_NO_CONTRACT
+    w[0] = nom[0] + draw[0];
+    w[1] = nom[1] + draw[1];
+    const float e = draw[2] * nom[2];
+    w[2] = nom[2] == kFtUnbounded ? nom[2] : e;
+}
+
+// Philox block of joint d's draws (words 0, 1, 2: damping, friction, effort)
+__device__ __forceinline__ uint32_t ft_joint_block(int d) { return kFtJointBlock | static_cast<uint32_t>(d); }
 
 #undef MW_FT_NO_CONTRACT
 

@@ -79,11 +79,12 @@ struct RunArgs {
     //             com[3], Io[6] about the origin (padded to kWparBaseWords)
     //   [16, ..)  the world's body block, stored compactly: the ChainF header
     //             (kWparHeadWords) and n BodyF, not the 48-body struct
-    // Only the inertial words differ between worlds; everything else in the
-    // body block (joint frames, limits, effort, damping) is a copy of the
+    // The inertial words (mw_set_link_params) and a joint's damping, friction
+    // and effort (mw_set_joint_dynamics) differ between worlds; everything else
+    // in the body block (joint frames, position limits) is a copy of the
     // shared ChainF, and every setter that rewrites the shared block
     // (mw_set_joint_param, mw_set_gravity: upload_params) rewrites all copies,
-    // keeping each world's inertial words.  FloatF (ground, shapes, gravity,
+    // keeping each world's own words.  FloatF (ground, shapes, gravity,
     // topology tables) is not duplicated and keeps one owner.  With wpar set the
     // kernel runs its WPAR instances, which imply the per-world friction read:
     // mu is then non-null as well.

@@ -41,7 +41,9 @@ int check_sim(const mw_sim* s, bool need_init) {
 }
 
 bool needs_cons(const mw_sim* s) {
-    return (s->h_params.flags & (mw::kHasLimits | mw::kHasFriction)) != 0 || s->servo_used;
+    // wpar_friction: some world's own friction word is non-zero where the
+    // nominal model may have none (mw_set_joint_dynamics, mw_floatenv_joints)
+    return (s->h_params.flags & (mw::kHasLimits | mw::kHasFriction)) != 0 || s->servo_used || s->wpar_friction;
 }
 bool needs_dual(const mw_sim* s) { return (s->h_params.flags & mw::kHasDamping) != 0; }
 
@@ -130,6 +132,14 @@ static float* link_words(float* rec, int link) {
     return link < 0 ? rec : rec + mw::kWparBaseWords + mw::kWparHeadWords + 40 * link + 16;
 }
 
+// the 40 words of body `dof` inside a world's record, and the three of them
+// that mw_set_joint_dynamics sets: damping, friction, effort
+static float* body_words(float* rec, int dof) { return rec + mw::kWparBaseWords + mw::kWparHeadWords + 40 * dof; }
+static constexpr int kJointWord[3] = {26, 27, 30};
+static_assert(offsetof(mw::BodyF, damping) == 26 * sizeof(float) && offsetof(mw::BodyF, friction) == 27 * sizeof(float) &&
+                  offsetof(mw::BodyF, effort) == 30 * sizeof(float),
+              "BodyF words 26, 27 and 30 are the joint's damping, friction and effort");
+
 // The per-world link parameters, every world at the model's nominal words:
 // allocate and fill, then publish (a failed call leaves the simulator as it
 // was).  The friction array comes with them: the kernel's per-world-parameter
@@ -174,18 +184,27 @@ int upload_link_params(mw_sim* s, int32_t w0, int32_t nw) {
 }
 
 // The shared parameter blocks were rebuilt (upload_params): every world's
-// record takes the new joint words and keeps its own inertial words.
-int refresh_link_params(mw_sim* s) {
+// record takes the new shared words and keeps its own -- the inertial words
+// and the three joint dynamics words (damping, friction, effort).  A joint
+// word that was never set per world is a copy of the shared one, so keeping it
+// is taking the shared value; the one word a shared setter changed
+// (mw_set_joint_param) is overwritten in every record: set_dof, set_word.
+int refresh_link_params(mw_sim* s, int set_dof = -1, int set_word = -1) {
     if (!s->d_wpar) return MW_OK;
-    if (s->env_inertia)
+    if (s->env_wpar())
         if (int rc = pull_link_params(s)) return rc;
     const size_t stride = static_cast<size_t>(s->wpar_stride);
-    std::vector<float> keep(10 * (static_cast<size_t>(s->n) + 1));
+    std::vector<float> keep(10 * (static_cast<size_t>(s->n) + 1)), keepj(3 * static_cast<size_t>(s->n));
     for (int32_t w = 0; w < s->W; ++w) {
         float* rec = s->h_wpar.data() + w * stride;
         for (int l = -1; l < s->n; ++l) std::memcpy(keep.data() + 10 * (l + 1), link_words(rec, l), 10 * sizeof(float));
+        for (int d = 0; d < s->n; ++d)
+            for (int k = 0; k < 3; ++k) keepj[3 * d + k] = body_words(rec, d)[kJointWord[k]];
         fill_link_record(s, rec);
         for (int l = -1; l < s->n; ++l) std::memcpy(link_words(rec, l), keep.data() + 10 * (l + 1), 10 * sizeof(float));
+        for (int d = 0; d < s->n; ++d)
+            for (int k = 0; k < 3; ++k)
+                if (!(d == set_dof && kJointWord[k] == set_word)) body_words(rec, d)[kJointWord[k]] = keepj[3 * d + k];
     }
     return upload_link_params(s, 0, s->W);
 }
@@ -386,19 +405,21 @@ void build_float(mw_sim* s) {
         F.body_path[i] = (uint64_t{1} << i) | (pa >= 0 ? F.body_path[pa] : uint64_t{0});
     }
     F.fanout = *std::max_element(children.begin(), children.end());
-    F.dual = 0;
+    // wpar_damping: some world's own damping word is non-zero (mw_set_joint_dynamics)
+    F.dual = s->wpar_damping ? 1 : 0;
     for (int i = 0; i < n; ++i)
         if (M.bodies[i].damping != 0.0) F.dual = 1;
     F.fixed = s->fixed_tree ? 1 : 0;
 }
 
-int upload_params(mw_sim* s) {
+int upload_params(mw_sim* s, int set_dof = -1, int set_word = -1) {
     if (s->float_tree) {
         build_params(s);
         build_float(s);
         MW_HIP(hipMemcpyAsync(s->d_params.get(), &s->h_params, sizeof(mw::ChainF), hipMemcpyHostToDevice, s->stream));
         MW_HIP(hipMemcpyAsync(s->d_float.get(), &s->h_float, sizeof(mw::FloatF), hipMemcpyHostToDevice, s->stream));
-        return refresh_link_params(s);  // the per-world copies of the body block follow the shared one
+        // the per-world copies of the body block follow the shared one
+        return refresh_link_params(s, set_dof, set_word);
     }
     if (s->floating) {
         build_free(s);
@@ -514,6 +535,15 @@ int state_words(const mw_sim* s) {
 }
 
 }  // namespace
+
+// wpar_friction / wpar_damping, the instance choices that follow per-world joint words
+int set_joint_dynamics_flags(mw_sim* s, bool friction, bool damping) {
+    s->wpar_friction = friction;
+    const bool changed = damping != s->wpar_damping;
+    s->wpar_damping = damping;
+    // FloatF::dual may follow: rebuild and upload the shared blocks (the records follow, words kept)
+    return changed ? upload_params(s) : MW_OK;
+}
 
 extern "C" {
 
@@ -1241,8 +1271,9 @@ int mw_set_joint_param(mw_sim* s, int32_t dof, int32_t which, double value) {
     // Joint.cpp:262-266: parameters can change only while the model was just created
     if (s->stepped) return fail(MW_ESTATE, "The model has been already processed and its parameters cannot be modified");
     mw::ChainBody& b = s->model.bodies[dof];
+    int word = -1;  // the per-world joint dynamics word this call overwrites in every record
     switch (which) {
-    case MW_PARAM_COULOMB_FRICTION: b.friction = value; break;
+    case MW_PARAM_COULOMB_FRICTION: b.friction = value; word = 27; break;
     case MW_PARAM_VISCOUS_FRICTION:
         // a damped floating tree runs on the wave kernel (dual recursion);
         // before the first step a lane-kernel model can still switch
@@ -1259,13 +1290,14 @@ int mw_set_joint_param(mw_sim* s, int32_t dof, int32_t which, double value) {
             s->wave = true;
         }
         b.damping = value;
+        word = 26;
         break;
-    case MW_PARAM_MAX_GENERALIZED_FORCE: b.effort = value; break;
+    case MW_PARAM_MAX_GENERALIZED_FORCE: b.effort = value; word = 30; break;
     case MW_PARAM_POSITION_LIMIT_MIN: b.lower = value; break;
     case MW_PARAM_POSITION_LIMIT_MAX: b.upper = value; break;
     default: return fail(MW_EINVAL, "unknown joint parameter");
     }
-    if (s->initialized) return upload_params(s);
+    if (s->initialized) return upload_params(s, dof, word);
     build_params(s);
     return MW_OK;
 }
@@ -1863,10 +1895,11 @@ static int check_link_params(const mw_sim* s, int32_t w0, int32_t nw, int32_t li
 
 int mw_set_link_params(mw_sim* s, int32_t w0, int32_t nw, int32_t link, const float* params) {
     if (int rc = check_link_params(s, w0, nw, link, params)) return rc;
-    if (s->env_inertia)
-        return fail(MW_ESTATE, "mw_set_link_params: a floating-base env with inertia randomisation owns this "
-                               "simulator's per-world link parameters (they live on the device); destroy the env "
-                               "first");
+    if (s->env_wpar())
+        return fail(MW_ESTATE, std::string("mw_set_link_params: a floating-base env with ") +
+                                   (s->env_inertia ? "inertia" : "joint") +
+                                   " randomisation owns this simulator's per-world link parameters (they live on "
+                                   "the device); destroy the env first");
     for (int32_t k = 0; k < nw; ++k) {
         const float* p = params + 10 * static_cast<size_t>(k);
         for (int e = 0; e < 10; ++e)
@@ -1883,7 +1916,7 @@ int mw_set_link_params(mw_sim* s, int32_t w0, int32_t nw, int32_t link, const fl
 
 int mw_link_params(mw_sim* s, int32_t w0, int32_t nw, int32_t link, float* params) {
     if (int rc = check_link_params(s, w0, nw, link, params)) return rc;
-    if (s->env_inertia) {  // the env's kernels write the records
+    if (s->env_wpar()) {  // the env's kernels write the records
         MW_HIP(hipSetDevice(s->cfg.device));
         if (int rc = pull_link_params(s)) return rc;
     }
@@ -1893,6 +1926,57 @@ int mw_link_params(mw_sim* s, int32_t w0, int32_t nw, int32_t link, float* param
                     s->d_wpar ? link_words(s->h_wpar.data() + static_cast<size_t>(w0 + k) * s->wpar_stride, link)
                               : nominal,
                     10 * sizeof(float));
+    return MW_OK;
+}
+
+// Per-world joint dynamics of one dof (wave kernel): damping, friction and
+// effort, words 26, 27 and 30 of the dof's BodyF in the same records.
+static int check_joint_dynamics(const mw_sim* s, int32_t w0, int32_t nw, int32_t dof, const void* params) {
+    if (int rc = check_link_params(s, w0, nw, 0, params)) return rc;
+    if (dof < 0 || dof >= s->n)
+        return fail(MW_EINVAL, "dof " + std::to_string(dof) + " out of range [0, " + std::to_string(s->n) + ")");
+    return MW_OK;
+}
+
+int mw_set_joint_dynamics(mw_sim* s, int32_t w0, int32_t nw, int32_t dof, const float* params) {
+    if (int rc = check_joint_dynamics(s, w0, nw, dof, params)) return rc;
+    if (s->env_wpar())
+        return fail(MW_ESTATE, std::string("mw_set_joint_dynamics: a floating-base env with ") +
+                                   (s->env_joints ? "joint" : "inertia") +
+                                   " randomisation owns this simulator's per-world link parameters (they live on "
+                                   "the device); destroy the env first");
+    bool friction = false, damping = false;
+    for (int32_t k = 0; k < nw; ++k) {
+        const float* p = params + 3 * static_cast<size_t>(k);
+        for (int e = 0; e < 3; ++e)
+            if (!std::isfinite(p[e])) return fail(MW_EINVAL, "the joint dynamics words must be finite");
+        if (!(p[0] >= 0.f)) return fail(MW_EINVAL, "the joint damping must be >= 0");
+        if (!(p[1] >= 0.f)) return fail(MW_EINVAL, "the joint friction must be >= 0");
+        if (!(p[2] > 0.f)) return fail(MW_EINVAL, "the joint effort limit must be > 0 (FLT_MAX: unbounded)");
+        damping = damping || p[0] != 0.f;
+        friction = friction || p[1] != 0.f;
+    }
+    MW_HIP(hipSetDevice(s->cfg.device));
+    if (int rc = alloc_link_params(s)) return rc;
+    for (int32_t k = 0; k < nw; ++k) {
+        float* b = body_words(s->h_wpar.data() + static_cast<size_t>(w0 + k) * s->wpar_stride, dof);
+        for (int e = 0; e < 3; ++e) b[kJointWord[e]] = params[3 * static_cast<size_t>(k) + e];
+    }
+    if (int rc = upload_link_params(s, w0, nw)) return rc;
+    return set_joint_dynamics_flags(s, s->wpar_friction || friction, s->wpar_damping || damping);
+}
+
+int mw_joint_dynamics(mw_sim* s, int32_t w0, int32_t nw, int32_t dof, float* params) {
+    if (int rc = check_joint_dynamics(s, w0, nw, dof, params)) return rc;
+    if (s->env_wpar()) {  // the env's kernels write the records
+        MW_HIP(hipSetDevice(s->cfg.device));
+        if (int rc = pull_link_params(s)) return rc;
+    }
+    for (int32_t k = 0; k < nw; ++k) {
+        const float* b = s->d_wpar ? body_words(s->h_wpar.data() + static_cast<size_t>(w0 + k) * s->wpar_stride, dof)
+                                   : reinterpret_cast<const float*>(&s->h_params.b[dof]);
+        for (int e = 0; e < 3; ++e) params[3 * static_cast<size_t>(k) + e] = b[kJointWord[e]];
+    }
     return MW_OK;
 }
 

@@ -144,6 +144,18 @@ struct mw_sim {
     // the device: mw_set_link_params fails with MW_ESTATE, mw_link_params reads
     // the device copy
     bool env_inertia = false;
+    // per-world joint dynamics (mw_set_joint_dynamics: BodyF::damping, friction
+    // and effort of the same records).  The host chooses two things from the
+    // nominal model that a world's own words can change, so both are sticky
+    // from the first non-zero word (or an env's draw, mw_floatenv_joints) on:
+    // friction rows need the wave kernel's CONS instance (needs_cons), damping
+    // the second recursion of its ABA (FloatF::dual, build_float)
+    bool wpar_friction = false;
+    bool wpar_damping = false;
+    // an env with joint randomisation (mw_floatenv_joints) writes those words on
+    // the device; like env_inertia it owns the records while it lives
+    bool env_joints = false;
+    bool env_wpar() const { return env_inertia || env_joints; }
     mw::pin_ptr<int[]> h_overflow;  // pinned copy read back with each synchronous run
     int64_t overflow_seen = 0;    // drops already reported
     // divergence detection: [W] sticky per-world flags + the uint64 count of
@@ -195,3 +207,5 @@ int pull_ground_friction(mw_sim* s);  // device copy -> host mirror (synchronise
 // words (and the friction array with them); device copy -> host mirror
 int alloc_link_params(mw_sim* s);
 int pull_link_params(mw_sim* s);
+// wpar_friction / wpar_damping (re-uploads FloatF when its dual flag may follow)
+int set_joint_dynamics_flags(mw_sim* s, bool friction, bool damping);

@@ -37,6 +37,9 @@ struct mw_vecenv {
     mw::dev_ptr<float[]> d_prev_action;
     mw::dev_ptr<uint32_t[]> d_air_steps;
     mw::dev_ptr<float[]> d_action_rate;
+    // joint randomisation (mw_floatenv_joints): the simulator's wpar_friction /
+    // wpar_damping before the first call turned the feature on
+    bool joints_saved[2] = {false, false};
 
     // the env's work (on its simulator's stream) drains before the members release their buffers
     ~mw_vecenv() { if (sim && sim->stream) (void)hipStreamSynchronize(sim->stream); }
@@ -393,6 +396,63 @@ int mw_floatenv_inertia(mw_vecenv* e, const mw_float_inertia_config* cfg, float*
     return MW_OK;
 }
 
+// Joint randomisation of a floating-base env: the post launch (and the
+// reset's) draws the damping, the friction and the effort limit of every
+// masked joint for the episode it starts into the same per-world records (the
+// JOINT instances of float_env_kernel.hip).  The run kernel's instance follows
+// what is drawn: friction needs CONS, damping FloatF::dual (set_joint_dynamics_flags).
+int mw_floatenv_joints(mw_vecenv* e, const mw_float_joint_config* cfg, float* joints_out, float* draw_out) {
+    if (!e || !cfg) return fail(MW_EINVAL, "null argument");
+    if (!e->floatenv) return fail(MW_ESTATE, "mw_floatenv_joints needs an env made by mw_floatenv_create");
+    if (e->was_reset) return fail(MW_ESTATE, "mw_floatenv_joints must be called before the first mw_vecenv_reset");
+    const float fields[] = {cfg->damping_lo, cfg->damping_hi, cfg->friction_lo,
+                            cfg->friction_hi, cfg->effort_scale_lo, cfg->effort_scale_hi};
+    for (float f : fields)
+        if (!std::isfinite(f)) return fail(MW_EINVAL, "every field of mw_float_joint_config must be finite");
+    if (!(cfg->damping_lo >= 0.f) || !(cfg->damping_hi >= cfg->damping_lo))
+        return fail(MW_EINVAL, "the damping range needs 0 <= damping_lo <= damping_hi");
+    if (!(cfg->friction_lo >= 0.f) || !(cfg->friction_hi >= cfg->friction_lo))
+        return fail(MW_EINVAL, "the joint friction range needs 0 <= friction_lo <= friction_hi");
+    const bool damping = cfg->damping_hi > 0.f, friction = cfg->friction_hi > 0.f, effort = cfg->effort_scale_hi > 0.f;
+    if (effort ? !(cfg->effort_scale_lo > 0.f && cfg->effort_scale_lo <= cfg->effort_scale_hi)
+               : (cfg->effort_scale_lo != 0.f || cfg->effort_scale_hi < 0.f))
+        return fail(MW_EINVAL, "the effort scale range needs 0 < effort_scale_lo <= effort_scale_hi (or both 0: off)");
+    mw_sim* s = e->sim;
+    const uint64_t all = s->n >= 64 ? ~uint64_t{0} : (uint64_t{1} << s->n) - 1u;
+    if (cfg->dof_mask & ~all) return fail(MW_EINVAL, "dof_mask names a joint the model does not have");
+    mw::FloatJointF& J = e->ftask.joints;
+    MW_HIP(hipSetDevice(s->cfg.device));
+    if (!damping && !friction && !effort) {  // everything off: the env as it was made
+        if (J.wpar) {
+            s->env_joints = false;
+            J = mw::FloatJointF{};
+            return set_joint_dynamics_flags(s, e->joints_saved[0], e->joints_saved[1]);
+        }
+        return MW_OK;
+    }
+    // the allocation first: a failed call leaves the env as it was
+    if (int rc = alloc_link_params(s)) return rc;
+    if (!J.wpar) {
+        e->joints_saved[0] = s->wpar_friction;
+        e->joints_saved[1] = s->wpar_damping;
+    }
+    if (int rc = set_joint_dynamics_flags(s, e->joints_saved[0] || friction, e->joints_saved[1] || damping)) return rc;
+    J = mw::FloatJointF{};
+    J.damping_lo = damping ? cfg->damping_lo : 0.f;
+    J.damping_hi = damping ? cfg->damping_hi : 0.f;
+    J.friction_lo = friction ? cfg->friction_lo : 0.f;
+    J.friction_hi = friction ? cfg->friction_hi : 0.f;
+    J.effort_lo = effort ? cfg->effort_scale_lo : 0.f;
+    J.effort_hi = effort ? cfg->effort_scale_hi : 0.f;
+    J.dof_mask = cfg->dof_mask ? cfg->dof_mask : all;
+    J.stride = s->wpar_stride;
+    J.wpar = s->d_wpar.get();
+    J.joints_out = joints_out;
+    J.draw_out = draw_out;
+    s->env_joints = true;
+    return MW_OK;
+}
+
 static int floatenv_reset(mw_vecenv* e, float* obs) {
     mw_sim* s = e->sim;
     e->was_reset = true;
@@ -431,11 +491,14 @@ void mw_vecenv_destroy(mw_vecenv* e) {
             (void)pull_ground_friction(s);
             s->env_friction = false;
         }
-        if (s->env_inertia) {
-            // ... and the last episode's link parameters
+        if (s->env_wpar()) {
+            // ... and the last episode's link parameters (inertial and joint
+            // words of one record); wpar_friction / wpar_damping stay as the
+            // env set them: the records keep the drawn words
             (void)hipSetDevice(s->cfg.device);
             (void)pull_link_params(s);
             s->env_inertia = false;
+            s->env_joints = false;
         }
     }
     delete e;

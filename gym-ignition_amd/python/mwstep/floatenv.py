@@ -22,9 +22,10 @@ resets: the host setters of ``env.sim`` that write them (``set("force_target"
 With pushes on it also owns the simulator's wrench buffer
 (``apply_world_wrench`` raises), with friction randomisation on the per-world
 ground friction (``set_ground_friction`` / ``set_ground_plane`` raise,
-``ground_friction()`` reads the device copy), with inertia randomisation on
-the per-world link parameters (``set_link_params`` raises, ``link_params()``
-reads the device copy).
+``ground_friction()`` reads the device copy), with inertia or joint
+randomisation on the per-world link parameters (``set_link_params``
+and ``set_joint_dynamics`` raise, ``link_params()`` and ``joint_dynamics()``
+read the device copy).
 
 ``task="locomotion"`` (``mw_floatenv_locomotion``) turns the env into a
 velocity-command task, still three launches per step: every world follows a
@@ -89,6 +90,10 @@ class FloatVecEnv:
                  mass_scale_range: Optional[Sequence[float]] = None,
                  payload_range: Optional[Sequence[float]] = None,
                  payload_box: Sequence[float] = (0.0, 0.0, 0.0),
+                 joint_damping_range: Optional[Sequence[float]] = None,
+                 joint_friction_range: Optional[Sequence[float]] = None,
+                 effort_scale_range: Optional[Sequence[float]] = None,
+                 joint_rand_dofs: Optional[Sequence] = None,
                  task: str = "forward",
                  command_ranges: Sequence[Sequence[float]] = ((0.0, 0.0), (0.0, 0.0), (0.0, 0.0)),
                  cmd_interval: int = 0, cmd_zero_prob: float = 0.0, cmd_min: float = 0.0,
@@ -126,6 +131,20 @@ class FloatVecEnv:
         ``[n_worlds, n + 5]`` (``info["inertia_draws"]``) the draws themselves:
         the ``n + 1`` scales, the payload mass and its position; both ``None``
         with the feature off.
+
+        Joint randomisation (``mw_floatenv_joints``), drawn anew at each reset
+        for every joint of ``joint_rand_dofs`` (names or dof indices; ``None``
+        = every joint): ``joint_damping_range`` ``(lo, hi)`` N m s/rad and
+        ``joint_friction_range`` ``(lo, hi)`` N m are added to the model's
+        values, ``effort_scale_range`` ``(lo, hi)`` scales the effort limit (an
+        unbounded one stays unbounded).  Joint friction costs one constraint
+        row per moving joint out of a world's 64 (``sim.constraint_overflow``
+        counts dropped rows): randomise, say, the legs only.  ``env.joint_dynamics``
+        ``[n_worlds, n, 3]`` (``info["joint_dynamics"]``) holds damping,
+        friction and effort limit in force for the current episode, in the
+        layout of ``Simulator.set_joint_dynamics``, and ``env.joint_draws``
+        ``[n_worlds, n, 3]`` (``info["joint_draws"]``) the draws themselves
+        (0, 0, 1 where nothing is drawn); both ``None`` with the feature off.
 
         ``task="locomotion"``: ``command_ranges`` holds the ``(lo, hi)`` of
         v_x, v_y (m/s) and the yaw rate (rad/s); a command is drawn every
@@ -258,6 +277,30 @@ class FloatVecEnv:
             ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
             N.check(N.lib().mw_floatenv_inertia(h, ctypes.byref(ic), ptr(self.inertial), ptr(self.inertia_draws)),
                     "mw_floatenv_inertia")
+
+        self.joint_dynamics = self.joint_draws = None
+        if joint_damping_range is not None or joint_friction_range is not None or effort_scale_range is not None:
+            dlo, dhi = (0.0, 0.0) if joint_damping_range is None else joint_damping_range
+            flo, fhi = (0.0, 0.0) if joint_friction_range is None else joint_friction_range
+            elo, ehi = (0.0, 0.0) if effort_scale_range is None else effort_scale_range
+            mask = 0
+            for d in (() if joint_rand_dofs is None else joint_rand_dofs):
+                di = sim.joint_names.index(d) if isinstance(d, str) else int(d)
+                if not 0 <= di < n:
+                    raise ValueError(f"joint_rand_dofs: dof {d!r} out of range [0, {n})")
+                mask |= 1 << di
+            if joint_rand_dofs is not None and mask == 0:
+                raise ValueError("joint_rand_dofs is empty (None = every joint)")
+            if dhi > 0 or fhi > 0 or ehi > 0:
+                nominal = np.stack([sim.joint_dynamics(d, [0])[0] for d in range(n)])
+                self.joint_dynamics = self._info["joint_dynamics"] = torch.from_numpy(
+                    np.tile(nominal, (n_worlds, 1, 1))).to(self.device)
+                self.joint_draws = self._info["joint_draws"] = torch.zeros((n_worlds, n, 3), **f32)
+                self.joint_draws[:, :, 2] = 1.0
+            jc = N.MwFloatJointConfig(dlo, dhi, flo, fhi, elo, ehi, mask)
+            ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+            N.check(N.lib().mw_floatenv_joints(h, ctypes.byref(jc), ptr(self.joint_dynamics), ptr(self.joint_draws)),
+                    "mw_floatenv_joints")
 
     # ------------------------------------------------------------------
     # what quadruped() / icub() add for task="locomotion" unless the caller sets it

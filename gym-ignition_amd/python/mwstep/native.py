@@ -138,6 +138,19 @@ class MwFloatInertiaConfig(ctypes.Structure):
     ]
 
 
+class MwFloatJointConfig(ctypes.Structure):
+    """mw_float_joint_config (include/mwstep.h)."""
+    _fields_ = [
+        ("damping_lo", ctypes.c_float),
+        ("damping_hi", ctypes.c_float),
+        ("friction_lo", ctypes.c_float),
+        ("friction_hi", ctypes.c_float),
+        ("effort_scale_lo", ctypes.c_float),
+        ("effort_scale_hi", ctypes.c_float),
+        ("dof_mask", ctypes.c_uint64),
+    ]
+
+
 # (name, restype, argtypes) of every symbol in include/mwstep.h
 _P = ctypes.c_void_p
 _I = ctypes.c_int32
@@ -209,6 +222,8 @@ SIGNATURES = [
     ("mw_ground_friction", ctypes.c_int, [_P, _I, _I, _D]),
     ("mw_set_link_params", ctypes.c_int, [_P, _I, _I, _I, ctypes.POINTER(ctypes.c_float)]),
     ("mw_link_params", ctypes.c_int, [_P, _I, _I, _I, ctypes.POINTER(ctypes.c_float)]),
+    ("mw_set_joint_dynamics", ctypes.c_int, [_P, _I, _I, _I, ctypes.POINTER(ctypes.c_float)]),
+    ("mw_joint_dynamics", ctypes.c_int, [_P, _I, _I, _I, ctypes.POINTER(ctypes.c_float)]),
     ("mw_enable_contacts", ctypes.c_int, [_P, _I]),
     ("mw_contacts_enabled", ctypes.c_int, [_P, _IP]),
     ("mw_get_contacts", ctypes.c_int, [_P, _I, _D, _I, _IP]),
@@ -234,6 +249,7 @@ SIGNATURES = [
     ("mw_floatenv_randomize", ctypes.c_int, [_P, ctypes.POINTER(MwFloatRandConfig), _P, _P]),
     ("mw_floatenv_locomotion", ctypes.c_int, [_P, ctypes.POINTER(MwFloatLocoConfig), _P]),
     ("mw_floatenv_inertia", ctypes.c_int, [_P, ctypes.POINTER(MwFloatInertiaConfig), _P, _P]),
+    ("mw_floatenv_joints", ctypes.c_int, [_P, ctypes.POINTER(MwFloatJointConfig), _P, _P]),
 ]
 
 # include/mwscene.h

@@ -324,6 +324,44 @@ class Simulator:
             k += nw
         return out
 
+    # -- per-world joint dynamics (mwstep.h: mw_set_joint_dynamics)
+    def _dof_index(self, dof) -> int:
+        return self.joint_names.index(dof) if isinstance(dof, str) else int(dof)
+
+    def set_joint_dynamics(self, dof, params, worlds=None) -> None:
+        """mw_set_joint_dynamics: viscous damping (N m s/rad), Coulomb friction
+        (N m) and effort limit (N m) of joint ``dof`` (name or index) per
+        world, ``[k, 3]`` or ``[3]`` for all ``k`` worlds of ``worlds``
+        (``None`` = every world).  The float32 words are what the kernel
+        reads, from the next run on; PID output limits derived from the
+        effort limit keep the nominal model."""
+        self._cache.clear()
+        di = self._dof_index(dof)
+        spans = self._worlds(worlds)
+        total = sum(nw for _, nw in spans)
+        v = np.ascontiguousarray(np.broadcast_to(np.asarray(params, dtype=np.float32), (total, 3)))
+        fp = ctypes.POINTER(ctypes.c_float)
+        k = 0
+        for w0, nw in spans:
+            N.check(N.lib().mw_set_joint_dynamics(self.handle, w0, nw, di, v[k:k + nw].ctypes.data_as(fp)),
+                    "set_joint_dynamics")
+            k += nw
+
+    def joint_dynamics(self, dof, worlds=None) -> np.ndarray:
+        """float32 ``[k, 3]``: damping, friction and effort limit the next run
+        will use (the model's nominal ones until ``set_joint_dynamics`` or an
+        env's draw changed them)."""
+        di = self._dof_index(dof)
+        spans = self._worlds(worlds)
+        out = np.zeros((sum(nw for _, nw in spans), 3), dtype=np.float32)
+        fp = ctypes.POINTER(ctypes.c_float)
+        k = 0
+        for w0, nw in spans:
+            N.check(N.lib().mw_joint_dynamics(self.handle, w0, nw, di, out[k:k + nw].ctypes.data_as(fp)),
+                    "joint_dynamics")
+            k += nw
+        return out
+
     @staticmethod
     def inertial_words(mass, com, inertia_about_com) -> np.ndarray:
         """The ten float32 words of a link from its mass, centre of mass and

@@ -309,6 +309,36 @@ int mw_ground_friction(mw_sim* sim, int32_t w0, int32_t nw, double* mu);
  * inertial words as they are. */
 int mw_set_link_params(mw_sim* sim, int32_t w0, int32_t nw, int32_t link, const float* params);
 int mw_link_params(mw_sim* sim, int32_t w0, int32_t nw, int32_t link, float* params);
+/* Per-world joint dynamics of one joint, worlds [w0, w0 + nw): params[nw][3]
+ * are the kernel's own float32 words of joint `dof`, set and read back bit for
+ * bit -- viscous damping (N m s/rad, >= 0), Coulomb friction (N m, >= 0) and
+ * the effort limit (N m, > 0; FLT_MAX is "unbounded"); all finite, dof and the
+ * world range in bounds, else MW_EINVAL and nothing changes.  They live in the
+ * records of mw_set_link_params and follow its rules: world-per-wavefront
+ * models only (MW_ESTATE otherwise), the first set allocates the storage,
+ * without it -- and for every world never set -- mw_joint_dynamics returns the
+ * nominal words, used from the next run on, parameters and not state.  While a
+ * floating-base env randomises inertias or joints (mw_floatenv_inertia,
+ * mw_floatenv_joints) it owns the records: mw_set_joint_dynamics and
+ * mw_set_link_params fail with MW_ESTATE and the getters read the env's device
+ * copy back.
+ *   Instance choice  the host picks the kernel's instance from the nominal
+ *       model, with two exceptions that are sticky from the first non-zero
+ *       word on: a friction word selects the instance with joint constraint
+ *       rows even where the nominal model has neither limits nor friction, and
+ *       a damping word turns on the second (non-implicit) recursion the
+ *       impulses of a damped model need, for every world of the simulator.
+ *   Shared setters  mw_set_joint_param(dof, which, value) keeps meaning "every
+ *       world": it overwrites that one word of that dof in every record and
+ *       keeps every other per-world joint word and all inertial words.
+ *   Host-derived quantities keep the nominal model: the output limits that
+ *       mw_set_joint_pid derives from the effort limit stay nominal; the clamp
+ *       the run applies to the joint force is the per-world word.
+ *   Row budget  friction adds one constraint row per moving joint to a world's
+ *       LCP, which holds 64 rows (8 foot points of the iCub already take 24);
+ *       rows beyond 64 are dropped and counted by mw_constraint_overflow. */
+int mw_set_joint_dynamics(mw_sim* sim, int32_t w0, int32_t nw, int32_t dof, const float* params);
+int mw_joint_dynamics(mw_sim* sim, int32_t w0, int32_t nw, int32_t dof, float* params);
 /* Model::enableContacts / contactsEnabled (Model.cpp:674-700). */
 int mw_enable_contacts(mw_sim* sim, int32_t enable);
 int mw_contacts_enabled(const mw_sim* sim, int32_t* enabled);
@@ -629,6 +659,44 @@ typedef struct {
     float payload_box[3];               /* m, half extents in the base frame */
 } mw_float_inertia_config;
 int mw_floatenv_inertia(mw_vecenv* env, const mw_float_inertia_config* cfg, float* inertial_dev, float* draws_dev);
+
+/* Joint randomisation of a floating-base env: per-world viscous damping,
+ * Coulomb friction and effort limit of the joints, drawn on the device
+ * wherever a reset is issued (every world on mw_vecenv_reset).  Call order and
+ * refusals are mw_floatenv_inertia's: after mw_floatenv_create and before the
+ * first mw_vecenv_reset (MW_ESTATE after it, or on another kind of env), in any
+ * order with the other three configuration calls; the step stays three
+ * launches; a refused call leaves the env as it was, everything off returns
+ * the env as made.  Joint d takes words 0, 1 and 2 of block 0x40000200 | d of
+ * the Philox counter (global world, episode, block, 0), so the draws are a
+ * pure function of (seed, global world, episode):
+ *   damping   a_d = U(damping_lo, damping_hi) N m s/rad added to the nominal
+ *             word.  On when damping_hi > 0; needs 0 <= lo <= hi.
+ *   friction  f_d = U(friction_lo, friction_hi) N m added to the nominal word,
+ *             likewise.
+ *   effort    s_d = U(effort_scale_lo, effort_scale_hi), effort = s_d effort0;
+ *             an unbounded nominal limit (FLT_MAX) is kept.  On when
+ *             effort_scale_hi > 0; needs 0 < lo <= hi.
+ * dof_mask bit d selects joint d (0 = every joint); a feature that is off and
+ * a joint outside the mask are skipped, not fed neutral values.  Friction adds
+ * one LCP row per moving joint: see the row budget of mw_set_joint_dynamics --
+ * the mask is there so that, say, only the legs are randomised.  The words go
+ * into the simulator's per-world records (mw_joint_dynamics reads them back;
+ * the instance choices of mw_set_joint_dynamics follow what is drawn) and the
+ * run that applies the reset reads them with it.  joints_dev float32
+ * [n_worlds, n_dofs, 3] is a caller-owned device buffer (may be NULL) that must
+ * outlive the env: every reset writes damping, friction and effort in force
+ * for the new episode (the nominal words of a joint outside the mask).
+ * draws_dev float32 [n_worlds, n_dofs, 3], likewise: a_d, f_d, s_d, and 0, 0, 1
+ * where a feature is off or the joint is outside the mask.  While such an env exists mw_set_joint_dynamics and
+ * mw_set_link_params fail with MW_ESTATE. */
+typedef struct {
+    float damping_lo, damping_hi;           /* N m s/rad added to the nominal; 0 <= lo <= hi; hi > 0 turns it on */
+    float friction_lo, friction_hi;         /* N m added to the nominal; likewise */
+    float effort_scale_lo, effort_scale_hi; /* factor on the nominal limit; 0 < lo <= hi; hi > 0 turns it on */
+    uint64_t dof_mask;                      /* bit d: joint d is drawn; 0 = every joint */
+} mw_float_joint_config;
+int mw_floatenv_joints(mw_vecenv* env, const mw_float_joint_config* cfg, float* joints_dev, float* draws_dev);
 
 #ifdef __cplusplus
 }

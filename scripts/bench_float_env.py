@@ -38,6 +38,16 @@ the mechanism: distinct parameter lines per wave instead of one shared block
 of the dynamics of robots that differ.  No world resets inside the timed
 windows (max_episode_steps 0), so the draw itself runs at reset() only.
 
+--joints adds two envs with the joint randomisation on (mw_floatenv_joints:
+the same WPAR instances of the run kernel reading every world's own body block,
+and the JOINT instance of the post kernel): env_jnom with effort_scale_range
+(1, 1) on one joint, whose records hold the nominal words -- the same physics
+as env on the run kernel's per-world instance, so env_jnom - env is the cost of
+the mechanism -- and env_joints with real ranges on the leg joints, whose
+difference from env_jnom is the cost of the dynamics: the damped model's
+second recursion and one friction row per moving masked joint.  No world
+resets inside the timed windows, so the draw itself runs at reset() only.
+
 Not a bench.py leg.  Prints one JSON line per model."""
 
 import argparse
@@ -54,6 +64,11 @@ LOCOMOTION = dict(task="locomotion", command_ranges=((-1.0, 1.0), (-0.5, 0.5), (
                   cmd_zero_prob=0.1, cmd_min=0.1, w_lin_z=2.0, w_ang_xy=0.05, w_action_rate=0.01, w_air_time=1.0)
 # --inertia: every link's mass within -20 % / +25 %, up to 5 kg on the base
 INERTIA = dict(mass_scale_range=(0.8, 1.25), payload_range=(0.0, 5.0), payload_box=(0.1, 0.1, 0.05))
+# --joints: up to 0.5 N m s/rad and 2 N m on the leg joints, 50 .. 100 % of the effort limit
+JOINTS = dict(joint_damping_range=(0.0, 0.5), joint_friction_range=(0.0, 2.0), effort_scale_range=(0.5, 1.0))
+JOINT_DOFS = {"quadruped": None,
+              "icub": [f"{s}_{j}" for s in ("l", "r")
+                       for j in ("hip_pitch", "hip_roll", "hip_yaw", "knee", "ankle_pitch", "ankle_roll")]}
 sys.path.insert(0, os.path.join(ROOT, "gym-ignition_amd", "python"))
 
 
@@ -145,6 +160,17 @@ def measure(torch, args, model, W):
             inert.reset()
         graphs["env_wpar"] = capture(torch, stream, lambda: wpar.step_raw(actions.data_ptr()), args.warmup)
         graphs["env_inertia"] = capture(torch, stream, lambda: inert.step_raw(actions.data_ptr()), args.warmup)
+    jnom = joints = None
+    if args.joints:
+        with torch.cuda.stream(stream):
+            jnom = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0, effort_scale_range=(1.0, 1.0),
+                                               joint_rand_dofs=[0])
+            jnom.reset()
+            joints = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0, joint_rand_dofs=JOINT_DOFS[model],
+                                                 **JOINTS)
+            joints.reset()
+        graphs["env_jnom"] = capture(torch, stream, lambda: jnom.step_raw(actions.data_ptr()), args.warmup)
+        graphs["env_joints"] = capture(torch, stream, lambda: joints.step_raw(actions.data_ptr()), args.warmup)
     times = {k: [] for k in graphs}
     for _ in range(args.rounds):
         for k, g in graphs.items():
@@ -195,6 +221,22 @@ def measure(torch, args, model, W):
                     "inertia_base_z_range_after": [round(float(zi.min()), 4), round(float(zi.max()), 4)]})
         wpar.close()
         inert.close()
+    if joints is not None:
+        n = env.action_dim
+        zj = joints.sim.base_pose()[:, 2]
+        same = bool((jnom.sim.get_state() == env.sim.get_state()).all())
+        words = joints.joint_dynamics.cpu().numpy()
+        out.update({"env_jnom_step_us": round(med["env_jnom"], 3), "env_joints_step_us": round(med["env_joints"], 3),
+                    "jnom_minus_env_us": round(med["env_jnom"] - med["env"], 3),
+                    "joints_minus_jnom_us": round(med["env_joints"] - med["env_jnom"], 3),
+                    "joints": JOINTS, "joint_rand_dofs": JOINT_DOFS[model], "jnom_state_equals_env_state": same,
+                    "link_parameter_bytes_per_world": 4 * (16 + 8 + 40 * n),
+                    "joint_word_and_draw_output_bytes_per_world": 4 * 6 * n,
+                    "friction_range_drawn": [round(float(words[:, :, 1].min()), 3), round(float(words[:, :, 1].max()), 3)],
+                    "joints_constraint_overflow": int(joints.sim.constraint_overflow()),
+                    "joints_base_z_range_after": [round(float(zj.min()), 4), round(float(zj.max()), 4)]})
+        jnom.close()
+        joints.close()
     env.close()
     sim.close()
     return out
@@ -212,6 +254,9 @@ def main():
     p.add_argument("--inertia", action="store_true",
                    help="also time envs with per-world link parameters: nominal words (env_wpar) and real ranges "
                         "(env_inertia)")
+    p.add_argument("--joints", action="store_true",
+                   help="also time envs with per-world joint dynamics: nominal words (env_jnom) and real ranges "
+                        "(env_joints)")
     p.add_argument("--task", choices=("forward", "locomotion"), default="forward",
                    help="locomotion: also time an env with the velocity-command task on (env_loco)")
     args = p.parse_args()
