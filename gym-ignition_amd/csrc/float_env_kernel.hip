@@ -31,6 +31,9 @@
 // each 32-lane half).
 #include <hip/hip_runtime.h>
 
+#include <array>
+#include <utility>
+
 #include "finite.hpp"
 #include "float_task.hpp"
 #include "kernels.hpp"
@@ -42,12 +45,6 @@ namespace dev {
 constexpr int kEnvTile = 64;      // worlds per block (lane = world)
 constexpr int kEnvThreads = 256;  // 4 waves share the tile's columns / rows
 constexpr int kEnvWaves = kEnvThreads / 64;
-static_assert(kFtBodyDamping * 4 == offsetof(BodyF, damping) && kFtBodyFriction * 4 == offsetof(BodyF, friction) &&
-                  kFtBodyEffort * 4 == offsetof(BodyF, effort),
-              "float_task.hpp restates the joint dynamics words of BodyF");
-static_assert(kFtWparBody0 == kWparBaseWords + kWparHeadWords && kFtBodyWords * 4 == sizeof(BodyF) &&
-                  kFtBodyInertial * 4 == offsetof(BodyF, mass),
-              "float_task.hpp restates the layout of RunArgs::wpar");
 
 // actions [W, n] -> out [n][W] (SimDev::cmd or ptgt), and sum_i a_i^2 per
 // world for the reward (asq [W]).  The value stored is the float32 the host
@@ -159,7 +156,7 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_action_kernel(const flo
 // (float_task.hpp; a feature that is off is skipped) -- from the nominal words
 // (P, the shared ChainF; T.inertia.base0) into the world's record of the run
 // kernel's per-world link parameters (T.inertia.wpar: the base's ten words,
-// words 16..25 of each BodyF), T.inertia.inertial_out and, the draws
+// each BodyF's ten from kBodyInertial on), T.inertia.inertial_out and, the draws
 // themselves, T.inertia.draw_out; the next run reads the record together with
 // the pending reset.  The blocks of four links go round the
 // waves starting at wave 1, so wave 0's chain takes one only from the 13th
@@ -168,8 +165,8 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_action_kernel(const flo
 // of the episode it starts -- joint d of T.joints.dof_mask takes a, f, s from
 // words 0..2 of block kFtJointBlock | d, damping = damping0 + a, friction =
 // friction0 + f, effort = s effort0 (ft_joint_words; the nominal words from P,
-// the shared ChainF) -- into words 26, 27 and 30 of the joint's BodyF in the
-// same record: one Philox call and three stores per joint.  A feature that is
+// the shared ChainF) -- into those three words of the joint's BodyF in the
+// same record (kBodyJointWord): one Philox call and three stores per joint.  A feature that is
 // off draws nothing and a joint outside the mask leaves its record alone; both
 // report the nominal words and the draws 0, 0, 1 (T.joints.joints_out,
 // draw_out).  The joints go round the waves starting at wave 1.
@@ -418,7 +415,7 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
                                 for (int e = 0; e < 3; ++e) draw[n + 2 + e] = pp[e];
                             }
                         }
-                        float* __restrict__ dst = k ? rec + kFtWparBody0 + (k - 1) * kFtBodyWords + kFtBodyInertial : rec;
+                        float* __restrict__ dst = k ? rec + kWparBody0 + (k - 1) * kWparBodyWords + kBodyInertial : rec;
 #pragma unroll
                         for (int e = 0; e < 10; ++e) {
                             dst[e] = wd[e];
@@ -432,7 +429,7 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
             const FloatJointF& J = T.joints;
             const uint32_t g = T.world_offset + static_cast<uint32_t>(w);
             const bool damp = J.damping_hi > 0.f, fric = J.friction_hi > 0.f, eff = J.effort_hi > 0.f;
-            float* __restrict__ rec = J.wpar + static_cast<size_t>(w) * J.stride + kFtWparBody0;
+            float* __restrict__ rec = J.wpar + static_cast<size_t>(w) * J.stride + kWparBody0;
             float* __restrict__ out = J.joints_out ? J.joints_out + static_cast<size_t>(w) * n * 3 : nullptr;
             float* __restrict__ draw = J.draw_out ? J.draw_out + static_cast<size_t>(w) * n * 3 : nullptr;
             for (int d = (wave + kEnvWaves - 1) % kEnvWaves; d < n; d += kEnvWaves) {
@@ -450,10 +447,10 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
                     if (damp) wd[0] = wn[0];
                     if (fric) wd[1] = wn[1];
                     if (eff) wd[2] = wn[2];
-                    float* __restrict__ dst = rec + d * kFtBodyWords;
-                    dst[kFtBodyDamping] = wd[0];
-                    dst[kFtBodyFriction] = wd[1];
-                    dst[kFtBodyEffort] = wd[2];
+                    float* __restrict__ dst = rec + d * kWparBodyWords;
+                    dst[kBodyDamping] = wd[0];
+                    dst[kBodyFriction] = wd[1];
+                    dst[kBodyEffort] = wd[2];
                 }
 #pragma unroll
                 for (int e = 0; e < 3; ++e) {
@@ -493,29 +490,35 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
 
 }  // namespace dev
 
-hipError_t launch_float_env_action(const float* actions, float* out, float* asq, uint8_t* div,
+hipError_t launch_float_env_action(const FloatTaskF& T, const float* actions, float* out, float* asq, uint8_t* div,
                                    unsigned long long* ndiv, int n, int W, hipStream_t st) {
+    const dim3 grid((W + dev::kEnvTile - 1) / dev::kEnvTile), block(dev::kEnvThreads);
     const size_t lds = static_cast<size_t>(dev::kEnvTile) * (n | 1) * sizeof(float);
-    hipLaunchKernelGGL(dev::float_env_action_kernel<false>, dim3((W + dev::kEnvTile - 1) / dev::kEnvTile),
-                       dim3(dev::kEnvThreads), lds, st, actions, out, asq, div, ndiv, n, W,
-                       dev::ActLocoArgs<false>{});
+    if (T.loco.on) {
+        dev::ActLocoArgs<true> A;
+        A.scale = T.loco.action_scale;
+        A.position = T.action_mode;
+        A.prev = T.loco.prev_action;
+        A.rate = T.loco.action_rate;
+        for (int d = 0; d < kMaxBodies; ++d) A.home_q[d] = T.home_q[d];
+        // two tiles: at most 2 x 64 x 49 words = 25 KB
+        hipLaunchKernelGGL(dev::float_env_action_kernel<true>, grid, block, 2 * lds, st, actions, out, asq, div, ndiv, n,
+                           W, A);
+    } else {
+        hipLaunchKernelGGL(dev::float_env_action_kernel<false>, grid, block, lds, st, actions, out, asq, div, ndiv, n, W,
+                           dev::ActLocoArgs<false>{});
+    }
     return hipGetLastError();
 }
 
-hipError_t launch_float_env_action_loco(const FloatTaskF& T, const float* actions, float* out, float* asq,
-                                        uint8_t* div, unsigned long long* ndiv, int n, int W, hipStream_t st) {
-    dev::ActLocoArgs<true> A;
-    A.scale = T.loco.action_scale;
-    A.position = T.action_mode;
-    A.prev = T.loco.prev_action;
-    A.rate = T.loco.action_rate;
-    for (int d = 0; d < kMaxBodies; ++d) A.home_q[d] = T.home_q[d];
-    // two tiles: at most 2 x 64 x 49 words = 25 KB
-    const size_t lds = 2 * static_cast<size_t>(dev::kEnvTile) * (n | 1) * sizeof(float);
-    hipLaunchKernelGGL(dev::float_env_action_kernel<true>, dim3((W + dev::kEnvTile - 1) / dev::kEnvTile),
-                       dim3(dev::kEnvThreads), lds, st, actions, out, asq, div, ndiv, n, W, A);
-    return hipGetLastError();
+// The 32 instances of the post kernel, bit k of the index the k-th template
+// argument: RAND, PUSH, LOCO, INERT, JOINT.
+using PostKernel = decltype(&dev::float_env_post_kernel<false, false, false, false, false>);
+template <size_t... I>
+constexpr std::array<PostKernel, sizeof...(I)> post_kernels(std::index_sequence<I...>) {
+    return {{dev::float_env_post_kernel<(I & 1) != 0, (I & 2) != 0, (I & 4) != 0, (I & 8) != 0, (I & 16) != 0>...}};
 }
+constexpr auto kPostKernels = post_kernels(std::make_index_sequence<32>{});
 
 hipError_t launch_float_env_post(const ChainF* P, const FloatTaskF& T, const SimDev& S, const FreeDev& D,
                                  const VecDev& V, const float* asq, float* obs, float* reward, uint8_t* done,
@@ -527,32 +530,8 @@ hipError_t launch_float_env_post(const ChainF* P, const FloatTaskF& T, const Sim
     // still inside the 64 KB a block gets without asking for more.
     const bool rand = T.rand.friction_hi > 0.f, push = T.rand.push_interval > 0u, loco = T.loco.on != 0u;
     const bool inert = T.inertia.wpar != nullptr, joint = T.joints.wpar != nullptr;
-#define MW_POST(R_, P_, L_, I_, J_)                                                                                  \
-    hipLaunchKernelGGL((dev::float_env_post_kernel<R_, P_, L_, I_, J_>), grid, block, lds, st, P, T, S, D, V, asq, obs, \
-                       reward, done, term_obs, n, W, reset_all)
-#define MW_POST_RP(L_, I_, J_)                           \
-    if (rand && push) MW_POST(true, true, L_, I_, J_);   \
-    else if (rand) MW_POST(true, false, L_, I_, J_);     \
-    else if (push) MW_POST(false, true, L_, I_, J_);     \
-    else MW_POST(false, false, L_, I_, J_)
-#define MW_POST_LI(J_)                 \
-    if (loco && inert) {               \
-        MW_POST_RP(true, true, J_);    \
-    } else if (loco) {                 \
-        MW_POST_RP(true, false, J_);   \
-    } else if (inert) {                \
-        MW_POST_RP(false, true, J_);   \
-    } else {                           \
-        MW_POST_RP(false, false, J_);  \
-    }
-    if (joint) {
-        MW_POST_LI(true)
-    } else {
-        MW_POST_LI(false)
-    }
-#undef MW_POST_LI
-#undef MW_POST_RP
-#undef MW_POST
+    hipLaunchKernelGGL(kPostKernels[rand | push << 1 | loco << 2 | inert << 3 | joint << 4], grid, block, lds, st, P, T,
+                       S, D, V, asq, obs, reward, done, term_obs, n, W, reset_all);
     return hipGetLastError();
 }
 

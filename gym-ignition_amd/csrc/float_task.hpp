@@ -31,6 +31,7 @@
 #include <cstdint>
 
 #include "chain_params.hpp"
+#include "world_params.hpp"
 
 namespace mw {
 
@@ -87,8 +88,6 @@ struct FloatInertiaF {
     float* inertial_out;           // [W, n + 1, 10] the words of the current episode (caller's, may be null)
     float* draw_out;               // [W, n + 5] the episode's draws: s_0 .. s_n, m_p, p xyz (caller's, may be null)
 };
-constexpr int kFtWparBody0 = 16 + 8;  // words of a record before its first BodyF (kernels.hpp)
-constexpr int kFtBodyWords = 40, kFtBodyInertial = 16;  // BodyF words; its ten inertial words start here
 constexpr uint32_t kFtScaleBlock = 0x40000100u;    // | k / 4, word k % 4: scale of link k (0 = the base), k <= 48
 constexpr uint32_t kFtPayloadBlock = 0x40000180u;  // r[0]: payload mass, r[1..3]: its position
 
@@ -105,7 +104,6 @@ struct FloatJointF {
     float* joints_out;               // [W, n, 3] damping, friction, effort of the current episode (caller's, may be null)
     float* draw_out;                 // [W, n, 3] the episode's draws a, f, s (caller's, may be null)
 };
-constexpr int kFtBodyDamping = 26, kFtBodyFriction = 27, kFtBodyEffort = 30;  // BodyF words
 constexpr uint32_t kFtJointBlock = 0x40000200u;  // | d, words 0..2: damping, friction, effort draw of joint d < 48
 constexpr float kFtUnbounded = 3.402823466e+38f;  // FLT_MAX: to_f32 of an infinite effort limit
 

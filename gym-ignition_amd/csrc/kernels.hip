@@ -774,7 +774,7 @@ template <int MAXN>
 static void wave_launch(bool cons, dim3 grid, dim3 block, hipStream_t st, const ChainF* P, const FloatF* F,
                         int n, const SimDev& S, const FreeDev& D, const PidF* pid, int W, const RunArgs& a,
                         int contacts, int* overflow) {
-    // WPAR implies WMU (sim.cpp allocates the friction array with the link
+    // WPAR implies WMU (world_params.cpp allocates the friction array with the link
     // parameters): 6 more instances, not 12
     const bool wmu = a.mu != nullptr, wpar = a.wpar != nullptr && wmu;
 #define MW_WAVE(C_, M_, P_)                                                                                         \

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "chain_params.hpp"
+#include "world_params.hpp"
 
 namespace mw {
 
@@ -74,26 +75,10 @@ struct RunArgs {
     const float* mu;
     // per-world link parameters in device memory (wave kernel,
     // mw_set_link_params), or null: every world takes the shared ChainF / FloatF.
-    // One record of wpar_stride words per world, wave-uniform like mu:
-    //   [0, 10)   the base's inertial words, as FloatF's first ten: mass,
-    //             com[3], Io[6] about the origin (padded to kWparBaseWords)
-    //   [16, ..)  the world's body block, stored compactly: the ChainF header
-    //             (kWparHeadWords) and n BodyF, not the 48-body struct
-    // The inertial words (mw_set_link_params) and a joint's damping, friction
-    // and effort (mw_set_joint_dynamics) differ between worlds; everything else
-    // in the body block (joint frames, position limits) is a copy of the
-    // shared ChainF, and every setter that rewrites the shared block
-    // (mw_set_joint_param, mw_set_gravity: upload_params) rewrites all copies,
-    // keeping each world's own words.  FloatF (ground, shapes, gravity,
-    // topology tables) is not duplicated and keeps one owner.  With wpar set the
-    // kernel runs its WPAR instances, which imply the per-world friction read:
-    // mu is then non-null as well.
+    // One record of wpar_stride words per world (world_params.hpp has the layout)
     const float* wpar;
     int wpar_stride;
 };
-constexpr int kWparBaseWords = 16;
-constexpr int kWparHeadWords = 8;  // offsetof(ChainF, b) / 4
-constexpr int wpar_stride_words(int n) { return kWparBaseWords + kWparHeadWords + 40 * n; }
 
 // Task description for the device-side env (see sim.cpp for the sources).
 struct TaskF {
@@ -191,19 +176,12 @@ hipError_t launch_vecenv_pid_group(const ChainF* P, int n, bool cons, bool dual,
 // diverged (SimDev::div / ndiv); the post launch follows the run: obs / reward
 // / done / counters, and the done worlds' pending resets for the next run.
 // reset_all: every world starts episode 0, only obs is written.
-hipError_t launch_float_env_action(const float* actions, float* out, float* asq, uint8_t* div,
-                                   unsigned long long* ndiv, int n, int W, hipStream_t st);
 // With the locomotion task on (mw_floatenv_locomotion, T.loco.on) both launches
-// run their LOCO instances: this action launch, which takes the task, keeps
-// the raw action (T.loco.prev_action) and sum (a_t - a_{t-1})^2
-// (T.loco.action_rate) and scales what it stores; the post launch appends
-// 12 + n words to every row.  Declared weak: the sanitizer harness links the
-// host layer against a stand-in of the launchers (tests/sanitize) that has no
-// locomotion launcher, and mw_floatenv_locomotion refuses to turn the task on
-// where the symbol is absent.
-hipError_t launch_float_env_action_loco(const struct FloatTaskF& T, const float* actions, float* out, float* asq,
-                                        uint8_t* div, unsigned long long* ndiv, int n, int W, hipStream_t st)
-    __attribute__((weak));
+// run their LOCO instances: the action launch keeps the raw action
+// (T.loco.prev_action) and sum (a_t - a_{t-1})^2 (T.loco.action_rate) and
+// scales what it stores; the post launch appends 12 + n words to every row.
+hipError_t launch_float_env_action(const struct FloatTaskF& T, const float* actions, float* out, float* asq,
+                                   uint8_t* div, unsigned long long* ndiv, int n, int W, hipStream_t st);
 // With randomisation on (mw_floatenv_randomize, T.rand) the post launch also
 // copies the base wrench the run applied (node 0 of D.wrench) into
 // T.rand.push_out and writes the next step's in its place (zeros where no push

@@ -53,7 +53,7 @@ bool needs_dual(const mw_sim* s) { return (s->h_params.flags & mw::kHasDamping) 
 int baked_id(const mw_sim* s) {
     const char* off = std::getenv("MWSTEP_DISABLE_BAKED");
     if (off && *off && *off != '0') return 0;
-    const size_t words = 8 + 40 * static_cast<size_t>(s->n);
+    const size_t words = static_cast<size_t>(mw::chain_words(s->n));
     if (words * 4 == sizeof(mw::baked::kCartpoleHost) &&
         std::memcmp(&s->h_params, &mw::baked::kCartpoleHost, words * 4) == 0)
         return mw::baked::kCartpoleId;
@@ -89,144 +89,7 @@ int alloc_env_wrench(mw_sim* s) {
     return MW_OK;
 }
 
-// The per-world friction array, every world at the current coefficient (the
-// float32 FloatF::mu holds): allocate, fill, then publish.
-int alloc_ground_friction(mw_sim* s) {
-    if (s->d_mu) return MW_OK;
-    const size_t W = static_cast<size_t>(s->W);
-    mw::dev_ptr<float[]> d;
-    MW_HIP(mw::dev_alloc(d, W * sizeof(float)));
-    s->h_mu.assign(W, static_cast<float>(s->ground_mu));
-    MW_HIP(hipMemcpyAsync(d.get(), s->h_mu.data(), W * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    MW_HIP(hipStreamSynchronize(s->stream));  // h_mu is pageable and rewritten by the setters
-    s->d_mu = std::move(d);
-    return MW_OK;
-}
-
-// device -> host mirror of the friction array (an env's kernels wrote it)
-int pull_ground_friction(mw_sim* s) {
-    if (!s->d_mu) return MW_OK;
-    MW_HIP(hipMemcpyAsync(s->h_mu.data(), s->d_mu.get(), static_cast<size_t>(s->W) * sizeof(float),
-                          hipMemcpyDeviceToHost, s->stream));
-    MW_HIP(hipStreamSynchronize(s->stream));
-    return MW_OK;
-}
-
-// One world's link parameter record from the shared blocks (kernels.hpp
-// RunArgs::wpar): the base's ten inertial words, the ChainF header, n BodyF.
-static void fill_link_record(const mw_sim* s, float* rec) {
-    std::memset(rec, 0, mw::kWparBaseWords * sizeof(float));
-    std::memcpy(rec, &s->h_float.mass, 10 * sizeof(float));
-    std::memcpy(rec + mw::kWparBaseWords, &s->h_params, mw::kWparHeadWords * sizeof(float));
-    std::memcpy(rec + mw::kWparBaseWords + mw::kWparHeadWords, s->h_params.b,
-                static_cast<size_t>(s->n) * sizeof(mw::BodyF));
-}
-static_assert(offsetof(mw::ChainF, b) == mw::kWparHeadWords * sizeof(float), "ChainF header words");
-static_assert(offsetof(mw::FloatF, Io) == 4 * sizeof(float) && offsetof(mw::FloatF, g) == 10 * sizeof(float),
-              "FloatF starts with the base's ten inertial words");
-static_assert(offsetof(mw::BodyF, mass) == 16 * sizeof(float) && offsetof(mw::BodyF, damping) == 26 * sizeof(float),
-              "BodyF words 16..25 are the body's ten inertial words");
-
-// the ten inertial words of `link` (-1 = the base) inside a world's record
-static float* link_words(float* rec, int link) {
-    return link < 0 ? rec : rec + mw::kWparBaseWords + mw::kWparHeadWords + 40 * link + 16;
-}
-
-// the 40 words of body `dof` inside a world's record, and the three of them
-// that mw_set_joint_dynamics sets: damping, friction, effort
-static float* body_words(float* rec, int dof) { return rec + mw::kWparBaseWords + mw::kWparHeadWords + 40 * dof; }
-static constexpr int kJointWord[3] = {26, 27, 30};
-static_assert(offsetof(mw::BodyF, damping) == 26 * sizeof(float) && offsetof(mw::BodyF, friction) == 27 * sizeof(float) &&
-                  offsetof(mw::BodyF, effort) == 30 * sizeof(float),
-              "BodyF words 26, 27 and 30 are the joint's damping, friction and effort");
-
-// The per-world link parameters, every world at the model's nominal words:
-// allocate and fill, then publish (a failed call leaves the simulator as it
-// was).  The friction array comes with them: the kernel's per-world-parameter
-// instances imply the per-world friction read.
-int alloc_link_params(mw_sim* s) {
-    if (s->d_wpar) return MW_OK;
-    const int stride = mw::wpar_stride_words(s->n);
-    const size_t W = static_cast<size_t>(s->W), words = W * stride;
-    mw::dev_ptr<float[]> d;
-    MW_HIP(mw::dev_alloc(d, words * sizeof(float)));
-    std::vector<float> h(words);
-    fill_link_record(s, h.data());
-    for (size_t w = 1; w < W; ++w) std::memcpy(h.data() + w * stride, h.data(), stride * sizeof(float));
-    MW_HIP(hipMemcpyAsync(d.get(), h.data(), words * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    MW_HIP(hipStreamSynchronize(s->stream));  // the mirror is pageable and rewritten by the setter
-    if (int rc = alloc_ground_friction(s)) return rc;
-    s->h_wpar = std::move(h);
-    s->wpar_stride = stride;
-    s->d_wpar = std::move(d);
-    return MW_OK;
-}
-
-// device -> host mirror of the link parameter records (an env's kernels wrote them)
-int pull_link_params(mw_sim* s) {
-    if (!s->d_wpar) return MW_OK;
-    MW_HIP(hipMemcpyAsync(s->h_wpar.data(), s->d_wpar.get(), s->h_wpar.size() * sizeof(float), hipMemcpyDeviceToHost,
-                          s->stream));
-    MW_HIP(hipStreamSynchronize(s->stream));
-    return MW_OK;
-}
-
 namespace {
-
-// host mirror -> device, worlds [w0, w0 + nw)
-int upload_link_params(mw_sim* s, int32_t w0, int32_t nw) {
-    if (nw <= 0) return MW_OK;
-    const size_t stride = static_cast<size_t>(s->wpar_stride);
-    MW_HIP(hipMemcpyAsync(s->d_wpar.get() + w0 * stride, s->h_wpar.data() + w0 * stride, nw * stride * sizeof(float),
-                          hipMemcpyHostToDevice, s->stream));
-    MW_HIP(hipStreamSynchronize(s->stream));  // the pageable mirror may be rewritten at once
-    return MW_OK;
-}
-
-// The shared parameter blocks were rebuilt (upload_params): every world's
-// record takes the new shared words and keeps its own -- the inertial words
-// and the three joint dynamics words (damping, friction, effort).  A joint
-// word that was never set per world is a copy of the shared one, so keeping it
-// is taking the shared value; the one word a shared setter changed
-// (mw_set_joint_param) is overwritten in every record: set_dof, set_word.
-int refresh_link_params(mw_sim* s, int set_dof = -1, int set_word = -1) {
-    if (!s->d_wpar) return MW_OK;
-    if (s->env_wpar())
-        if (int rc = pull_link_params(s)) return rc;
-    const size_t stride = static_cast<size_t>(s->wpar_stride);
-    std::vector<float> keep(10 * (static_cast<size_t>(s->n) + 1)), keepj(3 * static_cast<size_t>(s->n));
-    for (int32_t w = 0; w < s->W; ++w) {
-        float* rec = s->h_wpar.data() + w * stride;
-        for (int l = -1; l < s->n; ++l) std::memcpy(keep.data() + 10 * (l + 1), link_words(rec, l), 10 * sizeof(float));
-        for (int d = 0; d < s->n; ++d)
-            for (int k = 0; k < 3; ++k) keepj[3 * d + k] = body_words(rec, d)[kJointWord[k]];
-        fill_link_record(s, rec);
-        for (int l = -1; l < s->n; ++l) std::memcpy(link_words(rec, l), keep.data() + 10 * (l + 1), 10 * sizeof(float));
-        for (int d = 0; d < s->n; ++d)
-            for (int k = 0; k < 3; ++k)
-                if (!(d == set_dof && kJointWord[k] == set_word)) body_words(rec, d)[kJointWord[k]] = keepj[3 * d + k];
-    }
-    return upload_link_params(s, 0, s->W);
-}
-
-// host mirror -> device, worlds [w0, w0 + nw)
-int upload_ground_friction(mw_sim* s, int32_t w0, int32_t nw) {
-    if (nw <= 0) return MW_OK;
-    MW_HIP(hipSetDevice(s->cfg.device));
-    MW_HIP(hipMemcpyAsync(s->d_mu.get() + w0, s->h_mu.data() + w0, static_cast<size_t>(nw) * sizeof(float),
-                          hipMemcpyHostToDevice, s->stream));
-    MW_HIP(hipStreamSynchronize(s->stream));  // the pageable mirror may be rewritten at once
-    return MW_OK;
-}
-
-// ... and of the per-world ground friction while an env randomises it
-int check_not_env_friction(const mw_sim* s, const char* what) {
-    if (s && s->env_friction)
-        return fail(MW_ESTATE, std::string(what) + ": a floating-base env with friction randomisation owns this "
-                                                   "simulator's per-world ground friction (it lives on the "
-                                                   "device); destroy the env first");
-    return MW_OK;
-}
 
 // Host setters of commands / pending resets on a simulator that a
 // floating-base env drives: the env writes the same device arrays from its
@@ -412,7 +275,9 @@ void build_float(mw_sim* s) {
     F.fixed = s->fixed_tree ? 1 : 0;
 }
 
-int upload_params(mw_sim* s, int set_dof = -1, int set_word = -1) {
+}  // namespace
+
+int upload_params(mw_sim* s, int set_dof, int set_word) {
     if (s->float_tree) {
         build_params(s);
         build_float(s);
@@ -430,6 +295,8 @@ int upload_params(mw_sim* s, int set_dof = -1, int set_word = -1) {
     MW_HIP(hipMemcpyAsync(s->d_params.get(), &s->h_params, sizeof(mw::ChainF), hipMemcpyHostToDevice, s->stream));
     return MW_OK;
 }
+
+namespace {
 
 int pull_state(mw_sim* s) {
     if (!s->host_stale) return MW_OK;
@@ -535,15 +402,6 @@ int state_words(const mw_sim* s) {
 }
 
 }  // namespace
-
-// wpar_friction / wpar_damping, the instance choices that follow per-world joint words
-int set_joint_dynamics_flags(mw_sim* s, bool friction, bool damping) {
-    s->wpar_friction = friction;
-    const bool changed = damping != s->wpar_damping;
-    s->wpar_damping = damping;
-    // FloatF::dual may follow: rebuild and upload the shared blocks (the records follow, words kept)
-    return changed ? upload_params(s) : MW_OK;
-}
 
 extern "C" {
 
@@ -1273,7 +1131,7 @@ int mw_set_joint_param(mw_sim* s, int32_t dof, int32_t which, double value) {
     mw::ChainBody& b = s->model.bodies[dof];
     int word = -1;  // the per-world joint dynamics word this call overwrites in every record
     switch (which) {
-    case MW_PARAM_COULOMB_FRICTION: b.friction = value; word = 27; break;
+    case MW_PARAM_COULOMB_FRICTION: b.friction = value; word = mw::kBodyFriction; break;
     case MW_PARAM_VISCOUS_FRICTION:
         // a damped floating tree runs on the wave kernel (dual recursion);
         // before the first step a lane-kernel model can still switch
@@ -1290,9 +1148,9 @@ int mw_set_joint_param(mw_sim* s, int32_t dof, int32_t which, double value) {
             s->wave = true;
         }
         b.damping = value;
-        word = 26;
+        word = mw::kBodyDamping;
         break;
-    case MW_PARAM_MAX_GENERALIZED_FORCE: b.effort = value; word = 30; break;
+    case MW_PARAM_MAX_GENERALIZED_FORCE: b.effort = value; word = mw::kBodyEffort; break;
     case MW_PARAM_POSITION_LIMIT_MIN: b.lower = value; break;
     case MW_PARAM_POSITION_LIMIT_MAX: b.upper = value; break;
     default: return fail(MW_EINVAL, "unknown joint parameter");
@@ -1834,149 +1692,10 @@ int mw_set_ground_plane(mw_sim* s, int32_t enabled, double mu) {
     if (int own = check_not_env_friction(s, "mw_set_ground_plane")) return own;
     s->ground = enabled != 0;
     s->ground_mu = mu;
-    if (s->d_mu) {  // every world takes mu
-        std::fill(s->h_mu.begin(), s->h_mu.end(), static_cast<float>(mu));
-        if (int rc = upload_ground_friction(s, 0, s->W)) return rc;
-    }
+    if (int rc = fill_ground_friction(s, mu)) return rc;  // every world takes mu
     if (s->fbase() && s->initialized) return upload_params(s);
     if (s->float_tree && s->loaded) build_float(s);
     else if (s->floating && s->loaded) build_free(s);
-    return MW_OK;
-}
-
-// Per-world friction coefficients of the ground plane (wave kernel): the
-// float32 values the run kernel reads from mw_sim::d_mu, from the next run on.
-int mw_set_ground_friction(mw_sim* s, int32_t w0, int32_t nw, const double* mu) {
-    if (!s || !s->loaded) return fail(MW_ESTATE, "no model loaded");
-    if (!s->initialized) return fail(MW_ESTATE, "the simulator is not initialized");
-    if (!mu && nw > 0) return fail(MW_EINVAL, "null argument");
-    if (w0 < 0 || nw < 0 || w0 + nw > s->W) return fail(MW_EINVAL, "world range out of bounds");
-    if (!s->wave)
-        return fail(MW_ESTATE, "per-world ground friction on mw_sim needs the world-per-wavefront kernel (articulated "
-                               "floating bases, generic fixed-base trees); other models take one coefficient for "
-                               "all worlds (mw_set_ground_plane) or per-world friction through a scene "
-                               "(mw_scene_set_world_friction)");
-    if (int own = check_not_env_friction(s, "mw_set_ground_friction")) return own;
-    for (int32_t k = 0; k < nw; ++k)
-        if (!(mu[k] >= 0.0)) return fail(MW_EINVAL, "the friction coefficient must be >= 0");
-    MW_HIP(hipSetDevice(s->cfg.device));
-    if (int rc = alloc_ground_friction(s)) return rc;
-    for (int32_t k = 0; k < nw; ++k) s->h_mu[w0 + k] = static_cast<float>(mu[k]);
-    return upload_ground_friction(s, w0, nw);
-}
-
-int mw_ground_friction(mw_sim* s, int32_t w0, int32_t nw, double* mu) {
-    if (!s || !s->loaded) return fail(MW_ESTATE, "no model loaded");
-    if (!s->initialized) return fail(MW_ESTATE, "the simulator is not initialized");
-    if (!mu && nw > 0) return fail(MW_EINVAL, "null argument");
-    if (w0 < 0 || nw < 0 || w0 + nw > s->W) return fail(MW_EINVAL, "world range out of bounds");
-    if (s->env_friction) {  // the env's kernels write the array
-        MW_HIP(hipSetDevice(s->cfg.device));
-        if (int rc = pull_ground_friction(s)) return rc;
-    }
-    for (int32_t k = 0; k < nw; ++k) mu[k] = s->d_mu ? s->h_mu[w0 + k] : static_cast<float>(s->ground_mu);
-    return MW_OK;
-}
-
-// Per-world inertial words of one link (wave kernel): the float32 words the
-// run kernel reads from mw_sim::d_wpar, from the next run on.
-static int check_link_params(const mw_sim* s, int32_t w0, int32_t nw, int32_t link, const void* params) {
-    if (!s || !s->loaded) return fail(MW_ESTATE, "no model loaded");
-    if (!s->initialized) return fail(MW_ESTATE, "the simulator is not initialized");
-    if (!s->wave)
-        return fail(MW_ESTATE, "per-world link parameters need the world-per-wavefront kernel (articulated floating "
-                               "bases, mw_float_kernel == 2; generic fixed-base trees)");
-    if (!params && nw > 0) return fail(MW_EINVAL, "null argument");
-    if (w0 < 0 || nw < 0 || w0 + nw > s->W) return fail(MW_EINVAL, "world range out of bounds");
-    if (link < -1 || link >= s->n)
-        return fail(MW_EINVAL, "link " + std::to_string(link) + " out of range [-1, " + std::to_string(s->n) + ")");
-    return MW_OK;
-}
-
-int mw_set_link_params(mw_sim* s, int32_t w0, int32_t nw, int32_t link, const float* params) {
-    if (int rc = check_link_params(s, w0, nw, link, params)) return rc;
-    if (s->env_wpar())
-        return fail(MW_ESTATE, std::string("mw_set_link_params: a floating-base env with ") +
-                                   (s->env_inertia ? "inertia" : "joint") +
-                                   " randomisation owns this simulator's per-world link parameters (they live on "
-                                   "the device); destroy the env first");
-    for (int32_t k = 0; k < nw; ++k) {
-        const float* p = params + 10 * static_cast<size_t>(k);
-        for (int e = 0; e < 10; ++e)
-            if (!std::isfinite(p[e])) return fail(MW_EINVAL, "the link parameters must be finite");
-        if (!(p[0] > 0.f)) return fail(MW_EINVAL, "the link mass must be > 0");
-    }
-    MW_HIP(hipSetDevice(s->cfg.device));
-    if (int rc = alloc_link_params(s)) return rc;
-    for (int32_t k = 0; k < nw; ++k)
-        std::memcpy(link_words(s->h_wpar.data() + static_cast<size_t>(w0 + k) * s->wpar_stride, link),
-                    params + 10 * static_cast<size_t>(k), 10 * sizeof(float));
-    return upload_link_params(s, w0, nw);
-}
-
-int mw_link_params(mw_sim* s, int32_t w0, int32_t nw, int32_t link, float* params) {
-    if (int rc = check_link_params(s, w0, nw, link, params)) return rc;
-    if (s->env_wpar()) {  // the env's kernels write the records
-        MW_HIP(hipSetDevice(s->cfg.device));
-        if (int rc = pull_link_params(s)) return rc;
-    }
-    const float* nominal = link < 0 ? &s->h_float.mass : &s->h_params.b[link].mass;
-    for (int32_t k = 0; k < nw; ++k)
-        std::memcpy(params + 10 * static_cast<size_t>(k),
-                    s->d_wpar ? link_words(s->h_wpar.data() + static_cast<size_t>(w0 + k) * s->wpar_stride, link)
-                              : nominal,
-                    10 * sizeof(float));
-    return MW_OK;
-}
-
-// Per-world joint dynamics of one dof (wave kernel): damping, friction and
-// effort, words 26, 27 and 30 of the dof's BodyF in the same records.
-static int check_joint_dynamics(const mw_sim* s, int32_t w0, int32_t nw, int32_t dof, const void* params) {
-    if (int rc = check_link_params(s, w0, nw, 0, params)) return rc;
-    if (dof < 0 || dof >= s->n)
-        return fail(MW_EINVAL, "dof " + std::to_string(dof) + " out of range [0, " + std::to_string(s->n) + ")");
-    return MW_OK;
-}
-
-int mw_set_joint_dynamics(mw_sim* s, int32_t w0, int32_t nw, int32_t dof, const float* params) {
-    if (int rc = check_joint_dynamics(s, w0, nw, dof, params)) return rc;
-    if (s->env_wpar())
-        return fail(MW_ESTATE, std::string("mw_set_joint_dynamics: a floating-base env with ") +
-                                   (s->env_joints ? "joint" : "inertia") +
-                                   " randomisation owns this simulator's per-world link parameters (they live on "
-                                   "the device); destroy the env first");
-    bool friction = false, damping = false;
-    for (int32_t k = 0; k < nw; ++k) {
-        const float* p = params + 3 * static_cast<size_t>(k);
-        for (int e = 0; e < 3; ++e)
-            if (!std::isfinite(p[e])) return fail(MW_EINVAL, "the joint dynamics words must be finite");
-        if (!(p[0] >= 0.f)) return fail(MW_EINVAL, "the joint damping must be >= 0");
-        if (!(p[1] >= 0.f)) return fail(MW_EINVAL, "the joint friction must be >= 0");
-        if (!(p[2] > 0.f)) return fail(MW_EINVAL, "the joint effort limit must be > 0 (FLT_MAX: unbounded)");
-        damping = damping || p[0] != 0.f;
-        friction = friction || p[1] != 0.f;
-    }
-    MW_HIP(hipSetDevice(s->cfg.device));
-    if (int rc = alloc_link_params(s)) return rc;
-    for (int32_t k = 0; k < nw; ++k) {
-        float* b = body_words(s->h_wpar.data() + static_cast<size_t>(w0 + k) * s->wpar_stride, dof);
-        for (int e = 0; e < 3; ++e) b[kJointWord[e]] = params[3 * static_cast<size_t>(k) + e];
-    }
-    if (int rc = upload_link_params(s, w0, nw)) return rc;
-    return set_joint_dynamics_flags(s, s->wpar_friction || friction, s->wpar_damping || damping);
-}
-
-int mw_joint_dynamics(mw_sim* s, int32_t w0, int32_t nw, int32_t dof, float* params) {
-    if (int rc = check_joint_dynamics(s, w0, nw, dof, params)) return rc;
-    if (s->env_wpar()) {  // the env's kernels write the records
-        MW_HIP(hipSetDevice(s->cfg.device));
-        if (int rc = pull_link_params(s)) return rc;
-    }
-    for (int32_t k = 0; k < nw; ++k) {
-        const float* b = s->d_wpar ? body_words(s->h_wpar.data() + static_cast<size_t>(w0 + k) * s->wpar_stride, dof)
-                                   : reinterpret_cast<const float*>(&s->h_params.b[dof]);
-        for (int e = 0; e < 3; ++e) params[3 * static_cast<size_t>(k) + e] = b[kJointWord[e]];
-    }
     return MW_OK;
 }
 

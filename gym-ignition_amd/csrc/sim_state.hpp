@@ -1,5 +1,5 @@
 // sim_state.hpp -- the simulator behind an mw_sim handle and the helpers
-// sim.cpp shares with the batched envs (vecenv.cpp).  Internal, host only.
+// sim.cpp, world_params.cpp and the batched envs (vecenv.cpp) share.  Internal, host only.
 #pragma once
 
 #include "mwstep.h"
@@ -134,7 +134,7 @@ struct mw_sim {
     // setters fail with MW_ESTATE, mw_ground_friction reads the device copy
     bool env_friction = false;
     // per-world link parameters (mw_set_link_params, wave kernel): W records of
-    // wpar_stride words on the device (RunArgs::wpar, kernels.hpp) and their
+    // wpar_stride words on the device (RunArgs::wpar, world_params.hpp) and their
     // host mirror; allocated by the first call, together with d_mu (the
     // kernel's per-world-parameter instances read the friction per world too)
     mw::dev_ptr<float[]> d_wpar;
@@ -198,14 +198,19 @@ bool needs_cons(const mw_sim* s);
 bool needs_dual(const mw_sim* s);
 int baked_id(const mw_sim* s);
 mw::PidSet pid_set(const mw_sim* s);
-// allocate the device arrays an env's randomisation writes (zeroed wrenches
-// [6][n + 1][W]; friction [W] filled with the current coefficient)
+// the wrench array an env's pushes write (zeroed, [6][n + 1][W])
 int alloc_env_wrench(mw_sim* s);
+// rebuild and upload the shared parameter blocks; the per-world records follow
+// (set_dof, set_word: the joint dynamics word a shared setter overwrites in all)
+int upload_params(mw_sim* s, int set_dof = -1, int set_word = -1);
+// world_params.cpp.  alloc_*: on the first call, every world at the current
+// coefficient / nominal words; pull_*: device copy -> host mirror (synchronises)
 int alloc_ground_friction(mw_sim* s);
-int pull_ground_friction(mw_sim* s);  // device copy -> host mirror (synchronises)
-// the per-world link parameter records, every world at the model's nominal
-// words (and the friction array with them); device copy -> host mirror
+int pull_ground_friction(mw_sim* s);
+int fill_ground_friction(mw_sim* s, double mu);  // every world takes mu, if the array exists
+int check_not_env_friction(const mw_sim* s, const char* what);
 int alloc_link_params(mw_sim* s);
 int pull_link_params(mw_sim* s);
+int refresh_link_params(mw_sim* s, int set_dof, int set_word);
 // wpar_friction / wpar_damping (re-uploads FloatF when its dual flag may follow)
 int set_joint_dynamics_flags(mw_sim* s, bool friction, bool damping);

@@ -289,7 +289,6 @@ int mw_floatenv_locomotion(mw_vecenv* e, const mw_float_loco_config* cfg, float*
     if (!e || !cfg) return fail(MW_EINVAL, "null argument");
     if (!e->floatenv) return fail(MW_ESTATE, "mw_floatenv_locomotion needs an env made by mw_floatenv_create");
     if (e->was_reset) return fail(MW_ESTATE, "mw_floatenv_locomotion must be called before the first mw_vecenv_reset");
-    if (!mw::launch_float_env_action_loco) return fail(MW_ESTATE, "this build has no locomotion kernels");
     const float fields[] = {cfg->cmd_lo[0], cfg->cmd_lo[1], cfg->cmd_lo[2], cfg->cmd_hi[0], cfg->cmd_hi[1],
                             cfg->cmd_hi[2], cfg->cmd_zero_prob, cfg->cmd_min, cfg->action_scale, cfg->w_track_lin,
                             cfg->w_track_yaw, cfg->track_sigma, cfg->w_lin_z, cfg->w_ang_xy, cfg->w_action_rate,
@@ -466,12 +465,8 @@ static int floatenv_reset(mw_vecenv* e, float* obs) {
 static int floatenv_step(mw_vecenv* e, const void* a, float* o, float* r, uint8_t* d, float* to) {
     mw_sim* s = e->sim;
     const bool pos = e->ftask.action_mode == MW_FLOAT_ACTION_POSITION;
-    if (e->ftask.loco.on)
-        MW_HIP(mw::launch_float_env_action_loco(e->ftask, static_cast<const float*>(a), pos ? s->dev.ptgt : s->dev.cmd,
-                                                e->d_asq.get(), s->dev.div, s->dev.ndiv, s->n, s->W, s->stream));
-    else
-        MW_HIP(mw::launch_float_env_action(static_cast<const float*>(a), pos ? s->dev.ptgt : s->dev.cmd, e->d_asq.get(),
-                                           s->dev.div, s->dev.ndiv, s->n, s->W, s->stream));
+    MW_HIP(mw::launch_float_env_action(e->ftask, static_cast<const float*>(a), pos ? s->dev.ptgt : s->dev.cmd,
+                                       e->d_asq.get(), s->dev.div, s->dev.ndiv, s->n, s->W, s->stream));
     if (pos) s->ptgt_stale = true;  // the host mirror of the targets re-reads the device copy
     if (int rc = run_impl(s, 0, false)) return rc;
     MW_HIP(mw::launch_float_env_post(s->d_params.get(), e->ftask, s->dev, s->fdev, e->dev, e->d_asq.get(), o, r, d, to,

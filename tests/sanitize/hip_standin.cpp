@@ -132,8 +132,8 @@ hipError_t launch_vecenv_pid_step(const ChainF*, int, int, bool, bool, int, cons
 hipError_t launch_vecenv_pid_group(const ChainF*, int, bool, bool, const TaskF&, const SimDev&, const VecDev&,
                                    const GLaneTask*, const float*, float*, float*, uint8_t*, float*, int, float, int,
                                    int, hipStream_t) { return hipSuccess; }
-hipError_t launch_float_env_action(const float*, float*, float*, uint8_t*, unsigned long long*, int, int,
-                                   hipStream_t) { return hipSuccess; }
+hipError_t launch_float_env_action(const FloatTaskF&, const float*, float*, float*, uint8_t*, unsigned long long*, int,
+                                   int, hipStream_t) { return hipSuccess; }
 hipError_t launch_float_env_post(const ChainF*, const FloatTaskF&, const SimDev&, const FreeDev&, const VecDev&,
                                  const float*, float*, float*, uint8_t*, float*, int, int, int, hipStream_t) {
     return hipSuccess;

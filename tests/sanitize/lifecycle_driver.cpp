@@ -1,6 +1,6 @@
 // lifecycle_driver.cpp -- what the handles of the C ABI own, under ASan/UBSan.
 //
-// Links the host layer (sim.cpp, vecenv.cpp, scene.cpp, model.cpp, mesh.cpp)
+// Links the host layer (sim.cpp, world_params.cpp, vecenv.cpp, scene.cpp, model.cpp, mesh.cpp)
 // against hip_standin.cpp instead of the HIP runtime.  Every scenario runs
 // once cleanly, then once for each k = 0, 1, ... with the k-th creating call
 // (buffer, stream, event) failing, until a run no longer reaches its k-th
@@ -84,6 +84,62 @@ void env_case(const char* model, int kind, int randomize, Trace& t) {
     t.note(mw_vecenv_reset(e, obs.data()));
     for (int k = 0; k < 2; ++k)  // the second step finds the buffers a failed first one left
         t.note(mw_vecenv_step(e, act.data(), obs.data(), rew.data(), done.data(), tobs.data()));
+    mw_vecenv_destroy(e);
+    mw_destroy(s);
+}
+
+// The floating-base env of the quadruped with every configuration call that
+// allocates: pushes and friction (wrench and friction arrays), inertia and
+// joints (the per-world link parameter records; damping also re-uploads the
+// shared blocks), locomotion (the env's own buffers).  A call that fails leaves
+// the env without its feature, and the calls after it go on.
+void float_env_case(Trace& t) {
+    mw_sim* s = start_sim("quadruped.urdf", t);
+    int32_t n = 0;
+    (void)mw_dofs(s, &n);
+    t.note(mw_set_ground_plane(s, 1, 1.0));
+    t.note(mw_enable_contacts(s, 1));
+    const std::vector<float> home_q(n ? n : 1, 0.f);
+    const int32_t feet[4] = {1, 3, 5, 7};
+    mw_float_task_config tc{};
+    tc.action_mode = MW_FLOAT_ACTION_POSITION;
+    tc.max_episode_steps = 10;
+    tc.n_contact_links = 4;
+    tc.seed = 1;
+    tc.cos_tilt_max = -1.f;
+    tc.alive_bonus = 1.f;
+    tc.joint_noise = 0.05f;
+    tc.home_base[2] = 0.45f;
+    tc.home_base[3] = 1.f;
+    tc.home_q = home_q.data();
+    tc.contact_links = feet;
+    mw_vecenv* e = nullptr;
+    if (t.note(mw_floatenv_create(s, &tc, &e)) != MW_OK && e) t.bad = "a failed mw_floatenv_create returned a handle";
+    const size_t nd = static_cast<size_t>(n);
+    std::vector<float> push(W * 6), mu(W), inertial(W * (nd + 1) * 10), idraw(W * (nd + 5)), joints(W * nd * 3),
+        jdraw(W * nd * 3), command(W * 3);
+    const mw_float_rand_config rc = {4, 2, 20.f, 5.f, 0.4f, 1.2f};
+    t.note(mw_floatenv_randomize(e, &rc, push.data(), mu.data()));
+    const mw_float_inertia_config ic = {0.8f, 1.2f, 0.f, 2.f, {0.1f, 0.05f, 0.02f}};
+    t.note(mw_floatenv_inertia(e, &ic, inertial.data(), idraw.data()));
+    const mw_float_joint_config jc = {0.f, 0.5f, 0.f, 2.f, 0.5f, 1.f, 0};
+    t.note(mw_floatenv_joints(e, &jc, joints.data(), jdraw.data()));
+    mw_float_loco_config lc{};
+    lc.cmd_lo[0] = -1.f;
+    lc.cmd_hi[0] = 1.f;
+    lc.cmd_interval = 5;
+    lc.action_scale = 0.25f;
+    lc.w_track_lin = 1.f;
+    lc.track_sigma = 0.25f;
+    lc.w_air_time = 1.f;
+    lc.air_time_target = 0.1f;
+    lc.contact_force_min = 1.f;
+    t.note(mw_floatenv_locomotion(e, &lc, command.data()));
+    const size_t no = 25 + 3 * nd + 4;  // the locomotion row, the widest
+    std::vector<float> act(W * (nd ? nd : 1)), obs(W * no), tobs(W * no), rew(W);
+    std::vector<uint8_t> done(W);
+    t.note(mw_vecenv_reset(e, obs.data()));
+    for (int k = 0; k < 2; ++k) t.note(mw_vecenv_step(e, act.data(), obs.data(), rew.data(), done.data(), tobs.data()));
     mw_vecenv_destroy(e);
     mw_destroy(s);
 }
@@ -202,6 +258,7 @@ int main(int argc, char** argv) {
         env_case("cartpole.urdf", MW_TASK_CARTPOLE_DISCRETE, MW_RAND_MASS | MW_RAND_GRAVITY, t);
     });
     check("env_panda", [](Trace& t) { env_case("panda.urdf", MW_TASK_PANDA_POSITION_TRACKING, 0, t); });
+    check("env_float", [](Trace& t) { float_env_case(t); });
     check("scene_create", [](Trace& t) { scene_case(0, t); });
     check("scene_run", [](Trace& t) { scene_case(2, t); });
     check("scene_big", [](Trace& t) { scene_case(8, t); });

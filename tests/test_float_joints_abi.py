@@ -99,7 +99,7 @@ def test_python_layer_carries_the_arguments():
 
 
 # ---- the argument checks and the host-side rules, through a host build ----
-# The library's host layer (sim.cpp, vecenv.cpp, scene.cpp, model.cpp, mesh.cpp)
+# The library's host layer (sim.cpp, world_params.cpp, vecenv.cpp, scene.cpp, model.cpp, mesh.cpp)
 # over tests/sanitize/hip_standin.cpp, the stand-in for the HIP runtime that the
 # sanitizer lifecycle driver uses (plain g++, no sanitizer): device memory is
 # host memory and the kernel launchers do nothing, so everything the host decides
@@ -110,7 +110,8 @@ def host(N, tmp_path_factory):
     csrc = os.path.join(ROOT, "gym-ignition_amd", "csrc")
     out = str(tmp_path_factory.mktemp("hostlib") / "libmwhost.so")
     rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    srcs = [os.path.join(csrc, f) for f in ("sim.cpp", "vecenv.cpp", "scene.cpp", "model.cpp", "mesh.cpp")]
+    srcs = [os.path.join(csrc, f) for f in ("sim.cpp", "world_params.cpp", "vecenv.cpp", "scene.cpp", "model.cpp",
+                                                "mesh.cpp")]
     subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-w", "-D__HIP_PLATFORM_AMD__",
                     "-I", os.path.join(rocm, "include"), "-I", os.path.join(ROOT, "include"), "-I", csrc,
                     os.path.join(ROOT, "tests", "sanitize", "hip_standin.cpp"), *srcs, "-o", out], check=True)
@@ -221,6 +222,50 @@ def test_host_build_shared_setter_overwrites_one_word(N, host):
     back = np.zeros((W, 10), np.float32)
     assert L.mw_link_params(sim, 0, W, 1, _fp(back)) == N.MW_OK
     np.testing.assert_array_equal(back, mass)
+    L.mw_destroy(sim)
+
+
+def _all_records(N, L, sim, W, n):
+    """Every per-world word of every record: the ten inertial words of the base
+    and of each link, and each dof's damping, friction and effort."""
+    import numpy as np
+    inertial = np.zeros((n + 1, W, 10), np.float32)
+    for link in range(-1, n):
+        assert L.mw_link_params(sim, 0, W, link, _fp(inertial[link + 1])) == N.MW_OK
+    return inertial, _all_words(N, L, sim, W, n)
+
+
+def test_host_build_shared_setters_keep_a_world_with_both_kinds_of_words(N, host):
+    """One world holds its own inertial words (the base and link 3) and its own
+    joint words (dofs 3 and 6) in one record; mw_set_joint_param on dof 3 and
+    mw_set_gravity then rewrite every record from the shared blocks.  Every
+    per-world word of every world afterwards: the set ones kept, the one word the
+    shared setter names overwritten in all worlds, every other word nominal."""
+    import numpy as np
+    L, W, n, w = host, 3, 8, 1
+    sim = _host_sim(N, L, "quadruped", W)
+    inertial0, joints0 = _all_records(N, L, sim, W, n)       # nominal, before any storage exists
+    rng = np.random.default_rng(11)
+    want_i, want_j = inertial0.copy(), joints0.copy()
+    for link in (-1, 3):
+        words = (inertial0[link + 1, w] * rng.uniform(0.5, 2.0, 10)).astype(np.float32)
+        words[0] = abs(words[0]) + np.float32(0.25)
+        assert L.mw_set_link_params(sim, w, 1, link, _fp(words)) == N.MW_OK, L.mw_last_error()
+        want_i[link + 1, w] = words
+    for dof in (3, 6):
+        words = np.float32([rng.uniform(0.1, 0.5), rng.uniform(0.1, 2.0), rng.uniform(6, 60)])
+        assert L.mw_set_joint_dynamics(sim, w, 1, dof, _fp(words)) == N.MW_OK, L.mw_last_error()
+        want_j[dof, w] = words
+    got_i, got_j = _all_records(N, L, sim, W, n)
+    np.testing.assert_array_equal(got_i, want_i)
+    np.testing.assert_array_equal(got_j, want_j)
+    assert L.mw_set_joint_param(sim, 3, N.PARAM_VISCOUS_FRICTION, 0.125) == N.MW_OK, L.mw_last_error()
+    g = np.float64([0.5, 0.0, -3.7])
+    assert L.mw_set_gravity(sim, N.dptr(g)) == N.MW_OK
+    want_j[3, :, 0] = 0.125                                   # the named word, every world, the set one included
+    got_i, got_j = _all_records(N, L, sim, W, n)
+    np.testing.assert_array_equal(got_i, want_i)
+    np.testing.assert_array_equal(got_j, want_j)
     L.mw_destroy(sim)
 
 

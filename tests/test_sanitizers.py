@@ -13,8 +13,8 @@ on the MI355X pool).  tests/sanitize/Makefile builds four drivers with
   * hostdyn_san -- the device dynamics compiled for the host
     (tests/host_dyn/harness.cpp): chain / tree substeps with constraint rows
     and the floating-tree step with contacts;
-  * lifecycle_san -- the library's host layer (csrc/sim.cpp, vecenv.cpp,
-    scene.cpp) over a stand-in for the HIP runtime (hip_standin.cpp): every
+  * lifecycle_san -- the library's host layer (csrc/sim.cpp, world_params.cpp,
+    vecenv.cpp, scene.cpp) over a stand-in for the HIP runtime (hip_standin.cpp): every
     handle's life from create to destroy, cleanly and with each creating call
     (buffer, stream, event) failing in turn.
 
@@ -287,6 +287,9 @@ def test_device_dynamics_on_host_under_sanitizers(san, oracle, panda_file, cartp
 # order have not changed since, so fewer points would mean the driver no longer
 # reaches them.
 LIFECYCLE_POINTS = {"sim_cartpole": 10, "sim_cube": 20, "sim_icub": 20, "env_cartpole": 12, "env_panda": 12,
+                    # the quadruped's floating-base env with pushes, friction, inertia, joints and the
+                    # locomotion task: wrench and friction arrays, the link parameter records, the env's buffers
+                    "env_float": 28,
                     "scene_create": 21, "scene_run": 21, "scene_big": 24,
                     # contact readback across a capacity change (ensure_big: workspace, device and
                     # pinned contact block), read before the insertion or stale; the driver also
@@ -295,7 +298,7 @@ LIFECYCLE_POINTS = {"sim_cartpole": 10, "sim_cube": 20, "sim_icub": 20, "env_car
 
 
 def test_handles_own_their_resources_under_sanitizers(san):
-    """Simulator, CartPole env, Panda env and scenes at 8 worlds, once cleanly
+    """Simulator, CartPole env, Panda env, floating-base env and scenes at 8 worlds, once cleanly
     and once per creating call with that call failing (MW_EHIP and a message),
     every later call up to the destroy included: no sanitizer report, and after
     every destroy as many live buffers, streams and events as before."""
