@@ -16,7 +16,7 @@ the last observation of the finished one.
 from __future__ import annotations
 
 import ctypes
-from typing import Dict, Optional, Tuple
+from typing import Dict, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
@@ -47,13 +47,16 @@ class VecEnv:
                  device: int = 0, seed: int = 42, agent_rate: float = 1000.0,
                  physics_rate: float = 1000.0, max_episode_steps: int = 5000,
                  reward_cart_at_center: bool = True, model_file: Optional[str] = None,
-                 pgs_iters: int = 20, world_offset: int = 0, randomize: bool = False,
+                 pgs_iters: int = 20, world_offset: int = 0, randomize: Union[bool, int] = False,
                  mass_range: Tuple[float, float] = (-0.2, 0.2),
-                 gravity_normal: Tuple[float, float] = (-9.8, 0.2)):
+                 gravity_normal: Tuple[float, float] = (-9.8, 0.2),
+                 pose: Sequence[float] = (0, 0, 0, 1, 0, 0, 0)):
         """``randomize=True`` resamples every world's physics at each reset as the
         reference's CartPole randomizer does (randomizers/cartpole.py:51-56,
         100-135): body masses + max(U(*mass_range), 0), gravity z ~
-        N(*gravity_normal)."""
+        N(*gravity_normal).
+        ``randomize`` may also be an int mask of ``N.RAND_MASS`` / ``N.RAND_GRAVITY``: only those draws.
+        ``pose=(x, y, z, qw, qx, qy, qz)`` is the base pose handed to ``Simulator(pose=...)``."""
         torch = _torch()
         if task not in TASKS:
             raise ValueError(f"unknown task {task!r}; known: {sorted(TASKS)}")
@@ -69,7 +72,7 @@ class VecEnv:
             self._stream = torch.cuda.current_stream(self.device)
             self.sim = Simulator(model_file or get_model_file(model), n_worlds=n_worlds,
                                  step_size=1.0 / physics_rate, steps_per_run=steps_per_run,
-                                 device=device, pgs_iters=pgs_iters,
+                                 device=device, pgs_iters=pgs_iters, pose=pose,
                                  stream=self._stream.cuda_stream)
         if kind == N.TASK_PANDA_POSITION_TRACKING:
             from .models import PANDA_PID_GAINS_1000HZ
@@ -77,9 +80,11 @@ class VecEnv:
             for d, name in enumerate(self.sim.joint_names):
                 p, i, dd = PANDA_PID_GAINS_1000HZ[name]
                 self.sim.set_pid(d, [p, i, dd, -big, big, 0.0, -big, big])
+        # True: both bits; an int: the mask itself (False == 0: none)
+        both = N.RAND_MASS | N.RAND_GRAVITY
+        mask = (both if randomize else 0) if isinstance(randomize, (bool, np.bool_)) else int(randomize)
         cfg = N.MwTaskConfig(kind, max_episode_steps, 1 if reward_cart_at_center else 0,
-                             world_offset, seed & 0xFFFFFFFFFFFFFFFF,
-                             (N.RAND_MASS | N.RAND_GRAVITY) if randomize else 0,
+                             world_offset, seed & 0xFFFFFFFFFFFFFFFF, mask,
                              mass_range[0], mass_range[1], gravity_normal[0], gravity_normal[1], 0)
         self.randomize = randomize
         h = ctypes.c_void_p()

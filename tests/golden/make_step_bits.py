@@ -2,13 +2,22 @@
 step kernels produce, for tests/test_gpu_step_bits.py (which imports the cases
 and the runner from here).  Needs a GPU.
 
-    python tests/golden/make_step_bits.py [path/to/libmwstep.so [out.json]]
+    python tests/golden/make_step_bits.py [--add-missing] [path/to/libmwstep.so [out.json]]
 
-Run it against the library whose results are the reference: the committed
-fixture comes from the build of the commit BEFORE the step kernel took flat,
-preloaded arguments, so the test demands bit-identical results of that change
-and of every later one.  (MWSTEP_LIB, or the path argument, selects the
-library; the default is the in-tree build.)
+Run it against the library whose results are the reference.  The first 48
+cases of the committed fixture (the variants up to `discrete_rollout`) come
+from the build of the commit BEFORE the step kernel took flat, preloaded
+arguments, so the test demands bit-identical results of that change and of
+every later one.  The 36 cases of the randomised kernels (`*_randomized` of
+the other three tasks, and `discrete_randomized_` rollout / offset1000 /
+2substeps) were added with --add-missing from the build of the commit that
+added them, whose kernels still reproduce the first 48 bit for bit.
+(MWSTEP_LIB, or the path argument, selects the library; the default is the
+in-tree build.)
+
+--add-missing runs every case, refuses to write anything if a digest already
+in the fixture would change, and otherwise adds the cases the fixture lacks:
+the entries it had come out byte for byte as they were.
 
 A case is 120 closed-loop steps with max_episode_steps=40 and seeded actions,
 so TimeLimit, auto-reset, terminal_obs and the episode counter all act (the
@@ -40,6 +49,12 @@ VARIANTS = (
     ("discrete_offset1000", "CartPoleDiscreteBalancing", {"world_offset": 1000}, False),
     ("discrete_2substeps", "CartPoleDiscreteBalancing", {"physics_rate": 2000.0}, False),
     ("discrete_rollout", "CartPoleDiscreteBalancing", {}, True),
+    ("balancing_randomized", "CartPoleContinuousBalancing", {"randomize": True}, False),
+    ("swingup_randomized", "CartPoleContinuousSwingup", {"randomize": True}, False),
+    ("pendulum_randomized", "PendulumSwingUp", {"randomize": True}, False),
+    ("discrete_randomized_rollout", "CartPoleDiscreteBalancing", {"randomize": True}, True),
+    ("discrete_randomized_offset1000", "CartPoleDiscreteBalancing", {"randomize": True, "world_offset": 1000}, False),
+    ("discrete_randomized_2substeps", "CartPoleDiscreteBalancing", {"randomize": True, "physics_rate": 2000.0}, False),
 )
 CASES = [(f"{name}-W{W}-{'generic' if generic else 'baked'}", task, kw, rollout, W, generic)
          for name, task, kw, rollout in VARIANTS for W in WORLDS for generic in (False, True)]
@@ -90,8 +105,10 @@ def run_case(case):
 
 
 def main():
-    if len(sys.argv) > 1:
-        os.environ["MWSTEP_LIB"] = os.path.abspath(sys.argv[1])
+    argv = [a for a in sys.argv[1:] if a != "--add-missing"]
+    add_missing = len(argv) != len(sys.argv) - 1
+    if len(argv) > 0:
+        os.environ["MWSTEP_LIB"] = os.path.abspath(argv[0])
     sys.path.insert(0, os.path.join(ROOT, "gym-ignition_amd", "python"))
     from mwstep import native
     digests = {}
@@ -104,11 +121,20 @@ def main():
     os.environ.pop("MWSTEP_DISABLE_BAKED", None)
     doc = {"library_version": native.lib().mw_version().decode(), "steps": STEPS,
            "max_episode_steps": MAX_EPISODE_STEPS, "rollout_steps": ROLLOUT_STEPS, "digests": digests}
-    out = sys.argv[2] if len(sys.argv) > 2 else FIXTURE
+    out = argv[1] if len(argv) > 1 else FIXTURE
+    if add_missing:
+        with open(FIXTURE) as f:
+            old = json.load(f)
+        changed = sorted(k for k, v in old["digests"].items() if digests.get(k) != v)
+        if changed or any(old[k] != doc[k] for k in ("steps", "max_episode_steps", "rollout_steps")):
+            sys.exit(f"nothing written: this build does not reproduce {len(changed)} recorded cases: {changed}")
+        added = sorted(set(digests) - set(old["digests"]))
+        doc = dict(old, digests=dict(digests, **old["digests"]))   # the header and the old entries as they were
+        print(f"{len(old['digests'])} recorded cases reproduced; adding {len(added)}: {added}")
     with open(out, "w") as f:
         json.dump(doc, f, indent=1, sort_keys=True)
         f.write("\n")
-    print(f"wrote {out}: {len(digests)} cases from {native.LIB_PATH}")
+    print(f"wrote {out}: {len(doc['digests'])} cases from {native.LIB_PATH}")
 
 
 if __name__ == "__main__":

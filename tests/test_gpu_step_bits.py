@@ -13,6 +13,12 @@ physics, with world_offset=1000, with two substeps per step, and as a fused
 50-step rollout; 1, 65 (a partial second wave) and 16449 worlds (256-thread
 workgroups, partial last one); each on the constant-folded and on the generic
 kernel.  120 closed-loop steps with max_episode_steps=40.
+
+The randomised kernels have 36 more cases, recorded later from a build that
+reproduced the digests above: randomised physics on the other three tasks, and
+CartPole discrete with randomised physics as a fused rollout, with
+world_offset=1000 and with two substeps.  A digest shows a change; that the
+values are right is tests/test_gpu_randomized_matrix.py's business.
 """
 
 import importlib.util
