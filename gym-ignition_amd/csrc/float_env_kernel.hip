@@ -20,6 +20,15 @@
 // action-rate sum and writes the scaled command, the post launch appends the
 // body-frame block of the observation, draws the velocity commands and adds
 // the tracking / smoothness / air-time terms to the reward.
+// Observation noise and action latency (mw_floatenv_noise) stay inside the
+// same launches too.  The post launch adds amp[k] u to word k where it writes
+// a row of obs or terminal_obs out of its tile (ft_write_noisy; u from a Philox
+// stream keyed by the row's world, episode and step count), a block-uniform
+// runtime branch on the amplitude pointer rather than a sixth template flag;
+// reward, termination and the locomotion bookkeeping read the clean tile, and
+// the clean rows go to two optional buffers.  The action launch's DELAY
+// instances keep every world's last actions in a ring and hand the run the one
+// of d steps ago, d drawn per episode by the post launch that issues the reset.
 //
 // Both kernels are transposes between the row-major [W, k] tensors of the
 // agent and the [k][W] SoA arrays of the simulator.  A block of 256 threads
@@ -72,18 +81,64 @@ struct ActLocoArgs<true> {
     float home_q[kMaxBodies];
 };
 
-template <bool LOCO>
+// DELAY (the action latency of mw_floatenv_noise): every world keeps its last
+// R = delay_hi + 1 raw actions in L.ring [W][R][n], each row a contiguous span
+// of n words.  With t = L.steps[w] steps taken and d = L.delay[w] (the
+// episode's delay, left by the post launch that issued its reset), the thread
+// that stages word i of the tile stores it in the world's slot t % R and puts
+// the same word of slot (t - d) % R -- the action of step t - d, written by an
+// earlier launch where d > 0 -- into one more LDS tile, which the scaling and
+// the store to `out` then read instead of the raw one (the slots and what is
+// applied are worked out once per world into LDS first, and the stores to the
+// ring are a loop of their own behind the loads).  While t < d nothing is
+// read and the world receives the neutral command, home_q[j] in position mode
+// and 0 in torque mode (what action_scale * 0 gives): no slot an earlier
+// episode wrote is ever applied, so a reset leaves the ring alone.  sum a^2,
+// the action-rate term, A.prev and the non-finite test stay on the raw tile.
+template <bool DELAY>
+struct ActDelayArgs {};
+template <>
+struct ActDelayArgs<true> {
+    const uint32_t* steps;
+    const int32_t* delay;
+    float* ring;
+    uint32_t R;
+    int32_t position;
+    float home_q[kMaxBodies];
+};
+
+template <bool LOCO, bool DELAY>
 __global__ void __launch_bounds__(kEnvThreads) float_env_action_kernel(const float* __restrict__ actions,
                                                                        float* __restrict__ out,
                                                                        float* __restrict__ asq,
                                                                        uint8_t* __restrict__ div,
                                                                        unsigned long long* __restrict__ ndiv, int n,
-                                                                       int W, ActLocoArgs<LOCO> A) {
-    extern __shared__ float tile[];  // [kEnvTile][n | 1]; LOCO: then [kEnvTile][n | 1] of a_t - a_{t-1}
+                                                                       int W, ActLocoArgs<LOCO> A, ActDelayArgs<DELAY> L) {
+    // [kEnvTile][n | 1]; LOCO: then [kEnvTile][n | 1] of a_t - a_{t-1}; DELAY: then [kEnvTile][n | 1] of a_{t-d}
+    extern __shared__ float tile[];
     const int pitch = n | 1;
     const int w0 = blockIdx.x * kEnvTile;
     const int rows = min(kEnvTile, W - w0);
     const float* __restrict__ src = actions + static_cast<size_t>(w0) * n;
+    constexpr int kApplied = (LOCO ? 2 : 1) * kEnvTile;  // first row of the DELAY tile
+    // DELAY, per world of the tile: the ring row the step's action goes to, the
+    // row it applies, and what is applied -- 0 the action itself (d = 0), 1 the
+    // neutral command (t < d), 2 the ring's row
+    __shared__ uint32_t s_store[DELAY ? kEnvTile : 1];
+    __shared__ uint32_t s_read[DELAY ? kEnvTile : 1];
+    __shared__ uint8_t s_mode[DELAY ? kEnvTile : 1];
+    if constexpr (DELAY) {
+        if (static_cast<int>(threadIdx.x) < rows) {
+            const uint32_t t = L.steps[w0 + threadIdx.x], dl = static_cast<uint32_t>(L.delay[w0 + threadIdx.x]);
+            const bool kept = dl && !ft_delay_neutral(t, dl);
+            s_store[threadIdx.x] = ft_delay_slot(t, 0u, L.R);
+            // where no row is applied, one this launch does not write (R >= 2): the
+            // staging loop then loads without a branch and drops the value
+            s_read[threadIdx.x] = kept ? ft_delay_slot(t, dl, L.R) : ft_delay_slot(t + 1u, 0u, L.R);
+            s_mode[threadIdx.x] = dl ? (kept ? 2 : 1) : 0;
+        }
+        __syncthreads();
+    }
     // the tile's rows are one contiguous span of rows * n words
     for (int i = threadIdx.x; i < rows * n; i += kEnvThreads) {
         const int r = i / n, d = i - r * n;
@@ -94,15 +149,33 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_action_kernel(const flo
             tile[(kEnvTile + r) * pitch + d] = a - prev[i];
             prev[i] = a;
         }
+        if constexpr (DELAY) {
+            const float kept = L.ring[(static_cast<size_t>(w0 + r) * L.R + s_read[r]) * n + d];
+            tile[(kApplied + r) * pitch + d] = s_mode[r] == 2 ? kept : a;
+        }
     }
     __syncthreads();
+    if constexpr (DELAY) {
+        // the step's own action into its ring row, behind every load of the
+        // ring: a loop of stores alone, so neither loop waits on the other's memory
+        for (int i = threadIdx.x; i < rows * n; i += kEnvThreads) {
+            const int r = i / n, d = i - r * n;
+            L.ring[(static_cast<size_t>(w0 + r) * L.R + s_store[r]) * n + d] = tile[r * pitch + d];
+        }
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if (lane >= rows) return;
     const float* row = tile + lane * pitch;
+    const float* applied = DELAY ? tile + (kApplied + lane) * pitch : row;
+    bool neutral = false;
+    if constexpr (DELAY) neutral = s_mode[lane] == 1;
     for (int d = wave; d < n; d += kEnvWaves) {
-        float v = row[d];
+        float v = applied[d];
         if constexpr (LOCO) {
             if (A.scale > 0.f) v = A.position ? fmaf(A.scale, v, A.home_q[d]) : A.scale * v;
+        }
+        if constexpr (DELAY) {
+            if (neutral) v = L.position ? L.home_q[d] : 0.f;
         }
         out[static_cast<size_t>(d) * W + w0 + lane] = v;
     }
@@ -117,6 +190,55 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_action_kernel(const flo
             div[w0 + lane] = 1;
             atomicAdd(ndiv, 1ull);
         }
+    }
+}
+
+// The rows of the post kernel's tile written out with observation noise
+// (T.noise.amp): one thread per Philox block of four words, the (row, block)
+// pairs of the tile spread over the whole block, so a thread runs the ten
+// rounds a few times where a lane per word would run them once per row.  Word
+// k = 4 b + j leaves as clean + amp[k] u, u the noise unit of word j of block
+// b of the counter (global world, episode, b, 1 + t) -- a stream of its own:
+// every other draw has 0 in the fourth word -- with (episode, t) =
+// (s_episode[r] - back, s_t[r]); a word of amplitude zero keeps the clean
+// word's bits, and a block of such words draws nothing.  The clean words go to
+// `clean` (may be null); the tile stays clean.  only: the rows to write (null =
+// every row).
+__device__ __forceinline__ void ft_write_noisy(const FloatTaskF& T, const float* tile, int pitch, int rows, int w0,
+                                               float* __restrict__ dst, float* __restrict__ clean,
+                                               const uint8_t* only, const uint32_t* s_episode, uint32_t back,
+                                               const uint32_t* s_t) {
+    const int NO = T.n_obs, nb = (NO + 3) >> 2;
+    const float* __restrict__ amp = T.noise.amp;
+    for (int i = threadIdx.x; i < rows * nb; i += kEnvThreads) {
+        const int r = i / nb, b = i - r * nb;
+        if (only && !only[r]) continue;
+        const float* src = tile + r * pitch + 4 * b;
+        const size_t o = static_cast<size_t>(w0 + r) * NO + 4 * b;
+        const int m = min(4, NO - 4 * b);
+        float v[4], a[4];
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            v[j] = a[j] = 0.f;
+            if (j < m) {
+                v[j] = src[j];
+                a[j] = amp[4 * b + j];
+                if (clean) clean[o + j] = v[j];
+                any = any || a[j] != 0.f;
+            }
+        }
+        if (any) {
+            uint32_t x[4];
+            philox_ctr(T.seed_lo, T.seed_hi, T.world_offset + static_cast<uint32_t>(w0 + r), s_episode[r] - back,
+                       static_cast<uint32_t>(b), 1u + s_t[r], x);
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (a[j] != 0.f) v[j] = ft_noisy(v[j], a[j], ft_noise_unit(x[j]));
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (j < m) dst[o + j] = v[j];
     }
 }
 
@@ -182,7 +304,8 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
     extern __shared__ float tile[];  // [kEnvTile][n_obs | 1]: the observation rows
     __shared__ uint8_t s_done[kEnvTile];
     __shared__ uint32_t s_episode[kEnvTile];
-    __shared__ uint32_t s_steps[kEnvTile];  // PUSH: steps taken in the episode the next step belongs to
+    __shared__ uint32_t s_steps[kEnvTile];  // PUSH, noise: steps taken in the episode the next step belongs to
+    __shared__ uint32_t s_last[kEnvTile];   // noise: the step count a finished episode ended with
     __shared__ float s_cmd[LOCO ? 3 * kEnvTile : 1];                 // the command the step ran under
     __shared__ float s_pay[LOCO ? kMaxContactLinks * kEnvTile : 1];  // touchdown payment per link
     const int NO = T.n_obs, pitch = NO | 1;
@@ -192,6 +315,7 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int w = w0 + lane;
     const bool live = lane < rows;
+    const bool noisy = T.noise.amp != nullptr;  // block-uniform
     float* row = tile + lane * pitch;
     const size_t Ws = static_cast<size_t>(W);
     if (!reset_all) {
@@ -258,7 +382,7 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
         __syncthreads();
         if (wave == 0) {
             bool done = false;
-            uint32_t episode = 0u;
+            uint32_t episode = 0u, last = 0u;
             if (live) {
                 const bool term = ft_terminated(row[2], ft_tilt(row[4], row[5]), S.div[w] != 0, T.z_min, T.cos_tilt_max);
                 uint32_t steps = V.steps[w] + 1u;
@@ -275,6 +399,7 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
                 reward[w] = rew;
                 done_out[w] = done ? 1 : 0;
                 episode = V.episode[w];
+                last = steps;
                 if (done) {
                     episode += 1u;
                     steps = 0u;
@@ -284,19 +409,26 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
             }
             s_done[lane] = done ? 1 : 0;
             s_episode[lane] = episode;
-            if (PUSH) s_steps[lane] = live ? V.steps[w] : 0u;
+            if (PUSH || noisy) s_steps[lane] = live ? V.steps[w] : 0u;
+            if (noisy) s_last[lane] = last;
         }
         __syncthreads();
         // the finished episodes' last observation: row r of the tile, lanes across its words
-        for (int r = wave; r < rows; r += kEnvWaves)
-            if (s_done[r])
-                for (int k = lane; k < NO; k += 64) term_obs[static_cast<size_t>(w0 + r) * NO + k] = tile[r * pitch + k];
+        // (the noise of the finished episode at its final step count)
+        if (noisy) {
+            ft_write_noisy(T, tile, pitch, rows, w0, term_obs, T.noise.clean_term_obs, s_done, s_episode, 1u, s_last);
+        } else {
+            for (int r = wave; r < rows; r += kEnvWaves)
+                if (s_done[r])
+                    for (int k = lane; k < NO; k += 64)
+                        term_obs[static_cast<size_t>(w0 + r) * NO + k] = tile[r * pitch + k];
+        }
         __syncthreads();
     } else {
         if (wave == 0) {
             s_done[lane] = live ? 1 : 0;
             s_episode[lane] = 0u;
-            if (PUSH) s_steps[lane] = 0u;
+            if (PUSH || noisy) s_steps[lane] = 0u;
             if (live) {
                 V.episode[w] = 0u;
                 V.steps[w] = 0u;
@@ -377,6 +509,14 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
             const float mu = unif(r[1], T.rand.friction_lo, T.rand.friction_hi);
             T.rand.mu[w] = mu;
             if (T.rand.friction_out) T.rand.friction_out[w] = mu;
+        }
+        if (T.noise.ring && wave == 2) {
+            // the action delay of the episode this reset starts: the next action launch reads it
+            uint32_t r[4];
+            philox(T.seed_lo, T.seed_hi, T.world_offset + static_cast<uint32_t>(w), episode, r, kFtEpisodeBlock);
+            const int32_t dl = static_cast<int32_t>(ft_delay_draw(r[2], T.noise.delay_lo, T.noise.delay_hi));
+            T.noise.delay[w] = dl;
+            if (T.noise.delay_out) T.noise.delay_out[w] = dl;
         }
         if constexpr (INERT) {
             const FloatInertiaF& I = T.inertia;
@@ -484,30 +624,51 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
         for (int k = 0; k < 3; ++k) T.loco.command_out[static_cast<size_t>(w) * 3 + k] = row[NB + 9 + k];
     }
     __syncthreads();
+    // (the noise of the episode and step count the row belongs to: the updated counters)
+    if (noisy) {
+        ft_write_noisy(T, tile, pitch, rows, w0, obs, T.noise.clean_obs, nullptr, s_episode, 0u, s_steps);
+        return;
+    }
     for (int r = wave; r < rows; r += kEnvWaves)
         for (int k = lane; k < NO; k += 64) obs[static_cast<size_t>(w0 + r) * NO + k] = tile[r * pitch + k];
 }
 
 }  // namespace dev
 
-hipError_t launch_float_env_action(const FloatTaskF& T, const float* actions, float* out, float* asq, uint8_t* div,
-                                   unsigned long long* ndiv, int n, int W, hipStream_t st) {
+template <bool LOCO, bool DELAY>
+static void launch_action(const FloatTaskF& T, const float* actions, float* out, float* asq, uint8_t* div,
+                          unsigned long long* ndiv, int n, int W, hipStream_t st) {
     const dim3 grid((W + dev::kEnvTile - 1) / dev::kEnvTile), block(dev::kEnvThreads);
-    const size_t lds = static_cast<size_t>(dev::kEnvTile) * (n | 1) * sizeof(float);
-    if (T.loco.on) {
-        dev::ActLocoArgs<true> A;
+    // one tile, one more each for LOCO and DELAY: at most 3 x 64 x 49 words = 37 KB
+    const size_t lds = (1 + LOCO + DELAY) * static_cast<size_t>(dev::kEnvTile) * (n | 1) * sizeof(float);
+    dev::ActLocoArgs<LOCO> A;
+    dev::ActDelayArgs<DELAY> L;
+    if constexpr (LOCO) {
         A.scale = T.loco.action_scale;
         A.position = T.action_mode;
         A.prev = T.loco.prev_action;
         A.rate = T.loco.action_rate;
         for (int d = 0; d < kMaxBodies; ++d) A.home_q[d] = T.home_q[d];
-        // two tiles: at most 2 x 64 x 49 words = 25 KB
-        hipLaunchKernelGGL(dev::float_env_action_kernel<true>, grid, block, 2 * lds, st, actions, out, asq, div, ndiv, n,
-                           W, A);
-    } else {
-        hipLaunchKernelGGL(dev::float_env_action_kernel<false>, grid, block, lds, st, actions, out, asq, div, ndiv, n, W,
-                           dev::ActLocoArgs<false>{});
     }
+    if constexpr (DELAY) {
+        L.steps = T.noise.steps;
+        L.delay = T.noise.delay;
+        L.ring = T.noise.ring;
+        L.R = T.noise.delay_hi + 1u;
+        L.position = T.action_mode;
+        for (int d = 0; d < kMaxBodies; ++d) L.home_q[d] = T.home_q[d];
+    }
+    hipLaunchKernelGGL((dev::float_env_action_kernel<LOCO, DELAY>), grid, block, lds, st, actions, out, asq, div, ndiv, n,
+                       W, A, L);
+}
+
+hipError_t launch_float_env_action(const FloatTaskF& T, const float* actions, float* out, float* asq, uint8_t* div,
+                                   unsigned long long* ndiv, int n, int W, hipStream_t st) {
+    const bool loco = T.loco.on != 0u, delay = T.noise.ring != nullptr;
+    if (loco && delay) launch_action<true, true>(T, actions, out, asq, div, ndiv, n, W, st);
+    else if (loco) launch_action<true, false>(T, actions, out, asq, div, ndiv, n, W, st);
+    else if (delay) launch_action<false, true>(T, actions, out, asq, div, ndiv, n, W, st);
+    else launch_action<false, false>(T, actions, out, asq, div, ndiv, n, W, st);
     return hipGetLastError();
 }
 
@@ -526,7 +687,7 @@ hipError_t launch_float_env_post(const ChainF* P, const FloatTaskF& T, const Sim
     const size_t lds = static_cast<size_t>(dev::kEnvTile) * (T.n_obs | 1) * sizeof(float);
     const dim3 grid((W + dev::kEnvTile - 1) / dev::kEnvTile), block(dev::kEnvThreads);
     // The locomotion rows are 25 + 3 n + n_links words: at most (48 dofs, 8
-    // links) 64 x 177 words = 45 KB, with the kernel's 3.3 KB of static LDS
+    // links) 64 x 177 words = 45 KB, with the kernel's 3.6 KB of static LDS
     // still inside the 64 KB a block gets without asking for more.
     const bool rand = T.rand.friction_hi > 0.f, push = T.rand.push_interval > 0u, loco = T.loco.on != 0u;
     const bool inert = T.inertia.wpar != nullptr, joint = T.joints.wpar != nullptr;

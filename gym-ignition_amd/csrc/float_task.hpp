@@ -12,7 +12,9 @@
 // tests/host_float_joints/harness.cpp, and so is the arithmetic of the
 // locomotion task (mw_floatenv_locomotion: commands, projected gravity, the
 // air-time counter, the extra reward terms), built by
-// tests/host_float_loco/harness.cpp.
+// tests/host_float_loco/harness.cpp, and that of the observation noise and the
+// action latency (mw_floatenv_noise: the noise unit, the noisy word, the delay
+// draw and the ring's slots), built by tests/host_float_noise/harness.cpp.
 #pragma once
 
 #ifdef MW_HOST_TEST
@@ -52,7 +54,7 @@ struct FloatRandF {
 
 // Philox counter blocks of the randomisation draws: the reset draw uses
 // blocks 0 .. (n + 3) / 4 - 1 of the same (world, episode) counter.
-constexpr uint32_t kFtEpisodeBlock = 0x40000000u;  // r[0]: push phase, r[1]: friction
+constexpr uint32_t kFtEpisodeBlock = 0x40000000u;  // r[0]: push phase, r[1]: friction, r[2]: action delay
 constexpr uint32_t kFtPushBlock = 0x80000000u;     // | k: push k of the episode (fx, fy, tz)
 constexpr uint32_t kFtCmdBlock = 0xC0000000u;      // | k: command k of the episode (v_x, v_y, yaw rate, zero test)
 
@@ -107,6 +109,20 @@ struct FloatJointF {
 constexpr uint32_t kFtJointBlock = 0x40000200u;  // | d, words 0..2: damping, friction, effort draw of joint d < 48
 constexpr float kFtUnbounded = 3.402823466e+38f;  // FLT_MAX: to_f32 of an infinite effort limit
 
+// Observation noise and action latency of the floating-base env
+// (mw_floatenv_noise): the noise is on when amp is set, the latency when ring is.
+constexpr int kMaxActionDelay = 8;  // control steps; the ring holds delay_hi + 1 <= 9 rows per world
+struct FloatNoiseF {
+    const float* amp;          // [n_obs] amplitude of every observation word (device); null = no noise
+    float* clean_obs;          // [W, n_obs] the rows of obs before the noise (caller's, may be null)
+    float* clean_term_obs;     // [W, n_obs] likewise for terminal_obs, rows of done worlds only
+    uint32_t delay_lo, delay_hi;  // d = delay_lo + r[2] % (delay_hi - delay_lo + 1) per episode
+    float* ring;               // [W][delay_hi + 1][n] the raw actions of the last steps; null = no latency
+    int32_t* delay;            // [W] the delay of the current episode (the env's own: the action launch reads it)
+    const uint32_t* steps;     // [W] VecDev::steps for the action launch, whose launcher keeps its signature
+    int32_t* delay_out;        // [W] the same words (caller's, may be null)
+};
+
 // Task description of the floating-base env (kernel argument, by value).
 struct FloatTaskF {
     int32_t action_mode;     // 0 torque (SimDev::cmd), 1 position (SimDev::ptgt)
@@ -125,6 +141,7 @@ struct FloatTaskF {
     FloatLocoF loco;
     FloatInertiaF inertia;
     FloatJointF joints;
+    FloatNoiseF noise;
 };
 
 namespace dev {
@@ -199,6 +216,27 @@ __device__ __forceinline__ float ft_reward(const FloatTaskF& T, bool terminated,
 __device__ __forceinline__ float ft_unif(uint32_t x, float lo, float hi) {
     return lo + (hi - lo) * (static_cast<float>(x >> 8) * (1.f / 16777216.f));
 }
+
+// ---- observation noise and action latency (FloatNoiseF) ----
+// The unit of the noise, ft_unif(x, -1, 1): -1 + (x >> 8) 2^-23, a multiple of
+// 2^-23 in [-1, 1).  Every step is exact in float32 (a 24-bit integer, a power
+// of two, a difference of multiples of 2^-23 below 2), so the value does not
+// depend on whether the compiler fuses the product and the sum.
+__device__ __forceinline__ float ft_noise_unit(uint32_t x) { return ft_unif(x, -1.f, 1.f); }
+// clean + amp u in one rounding
+__device__ __forceinline__ float ft_noisy(float clean, float amp, float u) { return fmaf(amp, u, clean); }
+
+// The delay of an episode from word 2 of its episode block, lo <= hi.
+__device__ __forceinline__ uint32_t ft_delay_draw(uint32_t r2, uint32_t lo, uint32_t hi) {
+    return lo + r2 % (hi - lo + 1u);
+}
+// A ring of R rows per world: the step with t steps taken stores its action in
+// slot ft_delay_slot(t, 0, R) and applies the row of ft_delay_slot(t, d, R), the
+// action of step t - d -- while t < d the neutral command instead.  With d < R
+// the applied slot was last written at step t - d of this episode: the slots
+// written since are those of t - d + 1 .. t, all others modulo R.
+__device__ __forceinline__ bool ft_delay_neutral(uint32_t t, uint32_t d) { return t < d; }
+__device__ __forceinline__ uint32_t ft_delay_slot(uint32_t t, uint32_t d, uint32_t R) { return (t - d) % R; }
 
 // ---- inertia randomisation (FloatInertiaF) ----
 // A link's ten inertial words: mass, com xyz, Io xx yy zz xy xz yz about the

@@ -40,6 +40,12 @@ struct mw_vecenv {
     // joint randomisation (mw_floatenv_joints): the simulator's wpar_friction /
     // wpar_damping before the first call turned the feature on
     bool joints_saved[2] = {false, false};
+    // observation noise and action latency (mw_floatenv_noise): the amplitudes
+    // [n_obs], the ring of raw actions [W][delay_hi + 1][n] and the episodes'
+    // delays [W]
+    mw::dev_ptr<float[]> d_noise_amp;
+    mw::dev_ptr<float[]> d_action_ring;
+    mw::dev_ptr<int32_t[]> d_action_delay;
 
     // the env's work (on its simulator's stream) drains before the members release their buffers
     ~mw_vecenv() { if (sim && sim->stream) (void)hipStreamSynchronize(sim->stream); }
@@ -289,6 +295,9 @@ int mw_floatenv_locomotion(mw_vecenv* e, const mw_float_loco_config* cfg, float*
     if (!e || !cfg) return fail(MW_EINVAL, "null argument");
     if (!e->floatenv) return fail(MW_ESTATE, "mw_floatenv_locomotion needs an env made by mw_floatenv_create");
     if (e->was_reset) return fail(MW_ESTATE, "mw_floatenv_locomotion must be called before the first mw_vecenv_reset");
+    // it changes the width of the rows, which the noise amplitudes were checked against
+    if (e->ftask.noise.amp || e->ftask.noise.ring)
+        return fail(MW_ESTATE, "mw_floatenv_locomotion must be called before mw_floatenv_noise");
     const float fields[] = {cfg->cmd_lo[0], cfg->cmd_lo[1], cfg->cmd_lo[2], cfg->cmd_hi[0], cfg->cmd_hi[1],
                             cfg->cmd_hi[2], cfg->cmd_zero_prob, cfg->cmd_min, cfg->action_scale, cfg->w_track_lin,
                             cfg->w_track_yaw, cfg->track_sigma, cfg->w_lin_z, cfg->w_ang_xy, cfg->w_action_rate,
@@ -449,6 +458,70 @@ int mw_floatenv_joints(mw_vecenv* e, const mw_float_joint_config* cfg, float* jo
     J.joints_out = joints_out;
     J.draw_out = draw_out;
     s->env_joints = true;
+    return MW_OK;
+}
+
+// Observation noise and action latency of a floating-base env: the post launch
+// adds amp[k] u to the words of obs and terminal_obs as it writes them out and
+// draws the delay of every episode it starts; the action launch's DELAY
+// instance applies the action of that many steps ago from a per-world ring
+// (float_env_kernel.hip).
+static_assert(mw::kMaxActionDelay == MW_FLOAT_MAX_ACTION_DELAY, "the ring bound of float_task.hpp is the ABI's");
+int mw_floatenv_noise(mw_vecenv* e, const mw_float_noise_config* cfg, const float* amplitude, float* clean_obs,
+                      float* clean_terminal_obs, int32_t* delay_out) {
+    if (!e || !cfg) return fail(MW_EINVAL, "null argument");
+    if (!e->floatenv) return fail(MW_ESTATE, "mw_floatenv_noise needs an env made by mw_floatenv_create");
+    if (e->was_reset) return fail(MW_ESTATE, "mw_floatenv_noise must be called before the first mw_vecenv_reset");
+    if (cfg->delay_lo < 0 || cfg->delay_hi < cfg->delay_lo || cfg->delay_hi > mw::kMaxActionDelay)
+        return fail(MW_EINVAL, "the action delay range needs 0 <= delay_lo <= delay_hi <= " +
+                                   std::to_string(mw::kMaxActionDelay));
+    mw_sim* s = e->sim;
+    mw::FloatTaskF& T = e->ftask;
+    const size_t W = static_cast<size_t>(s->W), n = static_cast<size_t>(s->n), NO = static_cast<size_t>(T.n_obs);
+    if (amplitude) {
+        // the locomotion rows end with the command (3) and the last action (n): never noisy
+        const size_t exact0 = T.loco.on ? NO - 3 - n : NO;
+        for (size_t k = 0; k < NO; ++k) {
+            if (!std::isfinite(amplitude[k]) || amplitude[k] < 0.f)
+                return fail(MW_EINVAL, "every noise amplitude must be finite and >= 0 (word " + std::to_string(k) + ")");
+            if (k >= exact0 && amplitude[k] != 0.f)
+                return fail(MW_EINVAL, "the command and last-action words take no noise (word " + std::to_string(k) + ")");
+        }
+    }
+    const bool delay = cfg->delay_hi > 0;
+    MW_HIP(hipSetDevice(s->cfg.device));
+    // the allocations first: a failed call leaves the env as it was
+    mw::dev_ptr<float[]> amp, ring;
+    mw::dev_ptr<int32_t[]> dl;
+    if (amplitude) {
+        MW_HIP(mw::dev_alloc(amp, NO * sizeof(float)));
+        MW_HIP(hipMemcpy(amp.get(), amplitude, NO * sizeof(float), hipMemcpyHostToDevice));  // complete on return
+    }
+    if (delay) {
+        const size_t words = W * static_cast<size_t>(cfg->delay_hi + 1) * n;
+        MW_HIP(mw::dev_alloc(ring, words * sizeof(float)));
+        MW_HIP(mw::dev_alloc(dl, W * sizeof(int32_t)));
+        MW_HIP(hipMemsetAsync(ring.get(), 0, words * sizeof(float), s->stream));
+        MW_HIP(hipMemsetAsync(dl.get(), 0, W * sizeof(int32_t), s->stream));
+    }
+    e->d_noise_amp = std::move(amp);
+    e->d_action_ring = std::move(ring);
+    e->d_action_delay = std::move(dl);
+    mw::FloatNoiseF& N = T.noise;
+    N = mw::FloatNoiseF{};
+    if (amplitude) {
+        N.amp = e->d_noise_amp.get();
+        N.clean_obs = clean_obs;
+        N.clean_term_obs = clean_terminal_obs;
+    }
+    if (delay) {
+        N.delay_lo = static_cast<uint32_t>(cfg->delay_lo);
+        N.delay_hi = static_cast<uint32_t>(cfg->delay_hi);
+        N.ring = e->d_action_ring.get();
+        N.delay = e->d_action_delay.get();
+        N.steps = e->dev.steps;
+        N.delay_out = delay_out;
+    }
     return MW_OK;
 }
 

@@ -35,6 +35,12 @@ observation grows by projected gravity (3), body-frame linear (3) and angular
 n_contact_links`` words, ``env.obs_slices`` names them --, actions may be
 scaled around the home posture, and the reward gains command-tracking,
 vertical / roll-pitch velocity, action-rate and feet-air-time terms.
+
+``obs_noise=`` and ``action_delay_range=`` (``mw_floatenv_noise``) give the
+policy side of sim-to-real randomisation inside the same three launches:
+per-word uniform noise on ``obs`` and ``terminal_obs`` with the clean rows kept
+beside them (``env.clean_obs``), and a per-episode latency of up to 8 control
+steps between an action and the command the simulator receives.
 """
 
 from __future__ import annotations
@@ -43,6 +49,7 @@ import ctypes
 import math
 import os
 import xml.etree.ElementTree as ET
+from collections.abc import Mapping
 from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
@@ -100,7 +107,8 @@ class FloatVecEnv:
                  action_scale: float = 0.0, w_track_lin: float = 1.0, w_track_yaw: float = 0.5,
                  track_sigma: float = 0.25, w_lin_z: float = 0.0, w_ang_xy: float = 0.0,
                  w_action_rate: float = 0.0, w_air_time: float = 0.0, air_time_target: float = 0.0,
-                 contact_force_min: float = 1.0):
+                 contact_force_min: float = 1.0,
+                 obs_noise=None, action_delay_range: Optional[Sequence[int]] = None):
         """``model``: a shipped model's name or a URDF / SDF file.  ``home_q``
         (one value per dof) and ``home_base`` (x y z qw qx qy qz) are the reset
         state; ``pid_gains`` per dof ``(p, i, d)`` or the eight values of
@@ -161,7 +169,32 @@ class FloatVecEnv:
         for the next step, the same words as ``obs[:, env.obs_slices["command"]]``.
         With ``task="forward"`` ``env.command`` is ``None``; command ranges,
         ``cmd_interval``, ``action_scale`` and ``w_air_time`` are refused there
-        and the other locomotion weights have no effect."""
+        and the other locomotion weights have no effect.
+
+        Sensor noise and actuation latency (``mw_floatenv_noise``), both drawn
+        on the device inside the same three launches.  ``obs_noise`` maps group
+        names to amplitudes -- ``base_position``, ``base_orientation``,
+        ``base_linear_velocity``, ``base_angular_velocity``,
+        ``joint_positions``, ``joint_velocities``, ``contacts`` and, in the
+        locomotion task, ``gravity``, ``body_linear_velocity``,
+        ``body_angular_velocity`` (``env.noise_slices`` has their words) -- or
+        is a full vector of ``obs_dim`` amplitudes: word ``k`` of ``obs`` and
+        ``terminal_obs`` becomes ``clean + amplitude[k] * u``, ``u`` uniform in
+        [-1, 1), a pure function of (seed, global world, episode, step, k).
+        The command and last-action words take no noise; reward, termination
+        and the task's bookkeeping use the clean rows.  ``env.obs_noise``
+        ``[obs_dim]`` holds the amplitudes, ``env.clean_obs`` (also
+        ``info["clean_obs"]``) the rows before the noise -- what an asymmetric
+        critic is given -- and ``info["clean_terminal_obs"]`` those of
+        ``terminal_obs``.  ``action_delay_range`` ``(lo, hi)``, at most 8
+        control steps: every episode draws a delay ``d`` in it and the
+        simulator receives the action of ``d`` steps ago (scaled as usual),
+        during an episode's first ``d`` steps the neutral command -- ``home_q``
+        in position mode, zero torque otherwise; the reward's action terms and
+        the last-action words stay on the action just given.
+        ``env.action_delay`` ``[n_worlds]`` int32 (also
+        ``info["action_delay"]``) holds the current delays.  Each attribute is
+        ``None`` with its feature off."""
         torch = _torch()
         if action_mode not in ACTION_MODES:
             raise ValueError(f"unknown action_mode {action_mode!r}; known: {sorted(ACTION_MODES)}")
@@ -242,6 +275,14 @@ class FloatVecEnv:
             nb = 13 + 2 * n + nl
             self.obs_slices.update(gravity=slice(nb, nb + 3), body_velocity=slice(nb + 3, nb + 9),
                                    command=slice(nb + 9, nb + 12), last_action=slice(nb + 12, nb + 12 + n))
+        # the groups obs_noise names: the sensors behind the words
+        self.noise_slices = {"base_position": slice(0, 3), "base_orientation": slice(3, 7),
+                             "base_linear_velocity": slice(7, 10), "base_angular_velocity": slice(10, 13),
+                             "joint_positions": slice(13, 13 + n), "joint_velocities": slice(13 + n, 13 + 2 * n),
+                             "contacts": self.obs_slices["contacts"]}
+        if task == "locomotion":
+            self.noise_slices.update(gravity=slice(nb, nb + 3), body_linear_velocity=slice(nb + 3, nb + 6),
+                                     body_angular_velocity=slice(nb + 6, nb + 9))
         self.obs = torch.zeros((n_worlds, self.obs_dim), **f32)
         self.reward = torch.zeros((n_worlds,), **f32)
         self.done = torch.zeros((n_worlds,), dtype=torch.uint8, device=self.device)
@@ -301,6 +342,43 @@ class FloatVecEnv:
             ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
             N.check(N.lib().mw_floatenv_joints(h, ctypes.byref(jc), ptr(self.joint_dynamics), ptr(self.joint_draws)),
                     "mw_floatenv_joints")
+
+        self.obs_noise = self.clean_obs = self.clean_terminal_obs = self.action_delay = None
+        if obs_noise is not None or action_delay_range is not None:
+            amp = None
+            if obs_noise is not None:
+                amp = self._noise_vector(obs_noise)
+                self.obs_noise = torch.from_numpy(amp).to(self.device)
+                self.clean_obs = self._info["clean_obs"] = torch.zeros((n_worlds, self.obs_dim), **f32)
+                self.clean_terminal_obs = self._info["clean_terminal_obs"] = torch.zeros((n_worlds, self.obs_dim), **f32)
+            lo, hi = (0, 0) if action_delay_range is None else action_delay_range
+            if int(lo) != lo or int(hi) != hi:
+                raise ValueError("action_delay_range must hold two whole numbers of control steps")
+            if action_delay_range is not None:
+                self.action_delay = self._info["action_delay"] = torch.zeros((n_worlds,), dtype=torch.int32,
+                                                                              device=self.device)
+            nc = N.MwFloatNoiseConfig(int(lo), int(hi))
+            ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+            N.check(N.lib().mw_floatenv_noise(
+                h, ctypes.byref(nc), None if amp is None else amp.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                ptr(self.clean_obs), ptr(self.clean_terminal_obs), ptr(self.action_delay)), "mw_floatenv_noise")
+
+    def _noise_vector(self, obs_noise) -> np.ndarray:
+        """obs_noise (group name -> amplitude, or obs_dim values) as the float32 vector the library takes."""
+        if isinstance(obs_noise, Mapping):
+            amp = np.zeros(self.obs_dim, np.float32)
+            for name, value in obs_noise.items():
+                if name in ("command", "last_action"):
+                    raise ValueError(f"obs_noise: the {name} words take no noise")
+                if name not in self.noise_slices:
+                    raise ValueError(f"obs_noise: unknown group {name!r}; known: {sorted(self.noise_slices)}")
+                amp[self.noise_slices[name]] = value
+            return amp
+        amp = np.ascontiguousarray(obs_noise, dtype=np.float32)
+        if amp.shape != (self.obs_dim,):
+            raise ValueError(f"obs_noise must map group names to amplitudes or hold obs_dim ({self.obs_dim}) values, "
+                             f"got shape {amp.shape}")
+        return amp
 
     # ------------------------------------------------------------------
     # what quadruped() / icub() add for task="locomotion" unless the caller sets it

@@ -151,6 +151,17 @@ class MwFloatJointConfig(ctypes.Structure):
     ]
 
 
+class MwFloatNoiseConfig(ctypes.Structure):
+    """mw_float_noise_config (include/mwstep.h)."""
+    _fields_ = [
+        ("delay_lo", ctypes.c_int32),
+        ("delay_hi", ctypes.c_int32),
+    ]
+
+
+FLOAT_MAX_ACTION_DELAY = 8
+
+
 # (name, restype, argtypes) of every symbol in include/mwstep.h
 _P = ctypes.c_void_p
 _I = ctypes.c_int32
@@ -250,6 +261,8 @@ SIGNATURES = [
     ("mw_floatenv_locomotion", ctypes.c_int, [_P, ctypes.POINTER(MwFloatLocoConfig), _P]),
     ("mw_floatenv_inertia", ctypes.c_int, [_P, ctypes.POINTER(MwFloatInertiaConfig), _P, _P]),
     ("mw_floatenv_joints", ctypes.c_int, [_P, ctypes.POINTER(MwFloatJointConfig), _P, _P]),
+    ("mw_floatenv_noise", ctypes.c_int, [_P, ctypes.POINTER(MwFloatNoiseConfig), ctypes.POINTER(ctypes.c_float),
+                                         _P, _P, _P]),
 ]
 
 # include/mwscene.h

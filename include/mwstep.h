@@ -698,6 +698,51 @@ typedef struct {
 } mw_float_joint_config;
 int mw_floatenv_joints(mw_vecenv* env, const mw_float_joint_config* cfg, float* joints_dev, float* draws_dev);
 
+/* Observation noise and action latency of a floating-base env, both drawn on
+ * the device inside the step's three launches (no host copy, capturable), each
+ * off unless configured; with both off every output is what it was.  Call it
+ * after mw_floatenv_create and before the first mw_vecenv_reset (MW_ESTATE
+ * after it, or on another kind of env), and after mw_floatenv_locomotion,
+ * which changes the width of the rows: once a feature is on here
+ * mw_floatenv_locomotion fails with MW_ESTATE.  A refused call leaves the env
+ * as it was; a call with amplitude NULL and delay_hi 0 returns it as made.
+ *   noise    on when amplitude is not NULL: mw_vecenv_obs_dim host floats, all
+ *            finite and >= 0, and 0 on the command and last-action words of
+ *            the locomotion rows (MW_EINVAL otherwise).  Word k of a row of obs
+ *            or terminal_obs is clean[k] + amplitude[k] u in one fused
+ *            multiply-add, u = -1 + (x >> 8) 2^-23 in [-1, 1), x word k % 4 of
+ *            Philox4x32-10 keyed by the env's seed with the counter (global
+ *            world, episode, k / 4, 1 + t) -- every other draw has 0 in the
+ *            fourth word.  (episode, t) are the counters the row belongs to: a
+ *            row after a step the updated ones, a reset row (episode + 1, 0),
+ *            a terminal_obs row the finished episode and its final step count,
+ *            mw_vecenv_reset (0, 0).  A word of amplitude 0 keeps the clean
+ *            word's bits.  Reward, termination, the command schedule and the
+ *            air-time counters use the clean rows.  clean_obs_dev and
+ *            clean_terminal_obs_dev, float32 [n_worlds, obs_dim], are
+ *            caller-owned device buffers (either may be NULL) that must outlive
+ *            the env: the clean rows of obs, and of terminal_obs for the done
+ *            worlds, of every step and reset; ignored with the noise off.
+ *   latency  on when delay_hi > 0; needs 0 <= delay_lo <= delay_hi <=
+ *            MW_FLOAT_MAX_ACTION_DELAY.  Every episode draws d = delay_lo +
+ *            r[2] % (delay_hi - delay_lo + 1) from word 2 of its episode block
+ *            (0x40000000, see mw_floatenv_randomize) when its reset is issued.
+ *            The step with t steps taken in the episode keeps its action in
+ *            slot t % (delay_hi + 1) of a per-world ring and hands the run the
+ *            action of step t - d: scaled like an undelayed one (action_scale,
+ *            home_q), and while t < d the neutral command instead, home_q in
+ *            position mode and 0 in torque mode.  sum a^2, the action-rate
+ *            term, the last-action words and the non-finite test stay on the
+ *            action just submitted.  delay_dev int32 [n_worlds] is a
+ *            caller-owned device buffer (may be NULL) that must outlive the
+ *            env: every reset writes the new episode's d. */
+#define MW_FLOAT_MAX_ACTION_DELAY 8
+typedef struct {
+    int32_t delay_lo, delay_hi;     /* control steps, 0 <= lo <= hi <= 8; hi > 0 turns it on */
+} mw_float_noise_config;
+int mw_floatenv_noise(mw_vecenv* env, const mw_float_noise_config* cfg, const float* amplitude /* host, obs_dim words or NULL */,
+                      float* clean_obs_dev, float* clean_terminal_obs_dev, int32_t* delay_dev);
+
 #ifdef __cplusplus
 }
 #endif

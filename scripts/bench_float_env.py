@@ -48,6 +48,14 @@ difference from env_jnom is the cost of the dynamics: the damped model's
 second recursion and one friction row per moving masked joint.  No world
 resets inside the timed windows, so the draw itself runs at reset() only.
 
+--noise adds env_noise to the alternation: the step of another env with the
+observation noise on every sensor group and an action delay of 0..3 steps
+(mw_floatenv_noise: the post kernel's noisy write-out, one Philox block per
+four words of obs plus the clean rows, and the DELAY instance of the action
+kernel with its ring), fed the same home-posture targets -- the delayed and
+the neutral command are both the home posture, so the run does the same work
+-- and reports env_noise - env.
+
 Not a bench.py leg.  Prints one JSON line per model."""
 
 import argparse
@@ -69,6 +77,10 @@ JOINTS = dict(joint_damping_range=(0.0, 0.5), joint_friction_range=(0.0, 2.0), e
 JOINT_DOFS = {"quadruped": None,
               "icub": [f"{s}_{j}" for s in ("l", "r")
                        for j in ("hip_pitch", "hip_roll", "hip_yaw", "knee", "ankle_pitch", "ankle_roll")]}
+# --noise: encoder- and IMU-sized amplitudes on every sensor group, 0..3 control steps of latency
+NOISE = dict(obs_noise=dict(base_position=0.01, base_orientation=0.01, base_linear_velocity=0.1,
+                            base_angular_velocity=0.05, joint_positions=0.01, joint_velocities=0.5, contacts=2.0),
+             action_delay_range=(0, 3))
 sys.path.insert(0, os.path.join(ROOT, "gym-ignition_amd", "python"))
 
 
@@ -171,6 +183,12 @@ def measure(torch, args, model, W):
             joints.reset()
         graphs["env_jnom"] = capture(torch, stream, lambda: jnom.step_raw(actions.data_ptr()), args.warmup)
         graphs["env_joints"] = capture(torch, stream, lambda: joints.step_raw(actions.data_ptr()), args.warmup)
+    noisy = None
+    if args.noise:
+        with torch.cuda.stream(stream):
+            noisy = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0, **NOISE)
+            noisy.reset()
+        graphs["env_noise"] = capture(torch, stream, lambda: noisy.step_raw(actions.data_ptr()), args.warmup)
     times = {k: [] for k in graphs}
     for _ in range(args.rounds):
         for k, g in graphs.items():
@@ -237,6 +255,21 @@ def measure(torch, args, model, W):
                     "joints_base_z_range_after": [round(float(zj.min()), 4), round(float(zj.max()), 4)]})
         jnom.close()
         joints.close()
+    if noisy is not None:
+        zn = noisy.sim.base_pose()[:, 2]
+        moved = int((noisy.obs != noisy.clean_obs).sum().item())
+        delays = noisy.action_delay.cpu().numpy()
+        ring = W * (NOISE["action_delay_range"][1] + 1) * env.action_dim * 4
+        out.update({"env_noise_step_us": round(med["env_noise"], 3),
+                    "noise_minus_env_us": round(med["env_noise"] - med["env"], 3),
+                    "noise_minus_env_over_floor": round((med["env_noise"] - med["env"]) / med["floor"], 3),
+                    "noise_share_of_step": round((med["env_noise"] - med["env"]) / med["env_noise"], 4),
+                    "noise": {"obs_noise": NOISE["obs_noise"], "action_delay_range": list(NOISE["action_delay_range"])},
+                    "noisy_words_in_last_obs": moved, "delays_drawn": sorted(set(delays.tolist())),
+                    "noise_state_equals_env_state": bool((noisy.sim.get_state() == env.sim.get_state()).all()),
+                    "clean_row_bytes_per_step": W * env.obs_dim * 4, "ring_bytes": ring,
+                    "noise_base_z_range_after": [round(float(zn.min()), 4), round(float(zn.max()), 4)]})
+        noisy.close()
     env.close()
     sim.close()
     return out
@@ -257,6 +290,8 @@ def main():
     p.add_argument("--joints", action="store_true",
                    help="also time envs with per-world joint dynamics: nominal words (env_jnom) and real ranges "
                         "(env_joints)")
+    p.add_argument("--noise", action="store_true",
+                   help="also time an env with observation noise and action latency on (env_noise)")
     p.add_argument("--task", choices=("forward", "locomotion"), default="forward",
                    help="locomotion: also time an env with the velocity-command task on (env_loco)")
     args = p.parse_args()
