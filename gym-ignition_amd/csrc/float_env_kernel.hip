@@ -29,6 +29,15 @@
 // the clean rows go to two optional buffers.  The action launch's DELAY
 // instances keep every world's last actions in a ring and hand the run the one
 // of d steps ago, d drawn per episode by the post launch that issues the reset.
+// Shaping rewards, contact termination and episode statistics
+// (mw_floatenv_shaping) are one more block-uniform runtime branch of the post
+// launch (T.shape.on): during the gather every wave sums its share of the dofs
+// and links into partials in LDS (shape_gather), wave 0 combines them into the
+// ten terms, adds them to the reward, ors the termination links' loaded slots
+// into the termination and steps the running episode sums (shape_terms,
+// ft_shape_stats); the [W, 10] rows leave through two small LDS tiles as
+// contiguous spans.  In torque mode the action launch keeps the command it
+// stored in an array of the env, through a nullable argument.
 //
 // Both kernels are transposes between the row-major [W, k] tensors of the
 // agent and the [k][W] SoA arrays of the simulator.  A block of 256 threads
@@ -54,6 +63,11 @@ namespace dev {
 constexpr int kEnvTile = 64;      // worlds per block (lane = world)
 constexpr int kEnvThreads = 256;  // 4 waves share the tile's columns / rows
 constexpr int kEnvWaves = kEnvThreads / 64;
+static_assert(kEnvWaves == kShapeLanes, "a wave of the post kernel owns one partial of the shaping sums");
+constexpr int kShapePitch = kShapeTerms | 1;  // rows of the [kEnvTile][10] tiles in LDS
+// dynamic LDS of the post kernel's shaping branch: partial sums, two term tiles, hits
+constexpr size_t kShapeLds = (kEnvWaves * kShapeSums * kEnvTile + 2 * kEnvTile * kShapePitch) * sizeof(float) +
+                             kEnvWaves * kEnvTile;
 
 // actions [W, n] -> out [n][W] (SimDev::cmd or ptgt), and sum_i a_i^2 per
 // world for the reward (asq [W]).  The value stored is the float32 the host
@@ -107,13 +121,18 @@ struct ActDelayArgs<true> {
     float home_q[kMaxBodies];
 };
 
+// kept_cmd (mw_floatenv_shaping in torque mode, else null): the value stored
+// to `out` goes to this [n][W] array of the env as well -- the run zeroes
+// SimDev::cmd at its end, and the post launch's torque and power terms need
+// the command the run clamped.  A nullable argument, not another instance.
 template <bool LOCO, bool DELAY>
 __global__ void __launch_bounds__(kEnvThreads) float_env_action_kernel(const float* __restrict__ actions,
                                                                        float* __restrict__ out,
                                                                        float* __restrict__ asq,
                                                                        uint8_t* __restrict__ div,
                                                                        unsigned long long* __restrict__ ndiv, int n,
-                                                                       int W, ActLocoArgs<LOCO> A, ActDelayArgs<DELAY> L) {
+                                                                       int W, ActLocoArgs<LOCO> A, ActDelayArgs<DELAY> L,
+                                                                       float* __restrict__ kept_cmd) {
     // [kEnvTile][n | 1]; LOCO: then [kEnvTile][n | 1] of a_t - a_{t-1}; DELAY: then [kEnvTile][n | 1] of a_{t-d}
     extern __shared__ float tile[];
     const int pitch = n | 1;
@@ -178,6 +197,8 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_action_kernel(const flo
             if (neutral) v = L.position ? L.home_q[d] : 0.f;
         }
         out[static_cast<size_t>(d) * W + w0 + lane] = v;
+        // the shaping terms' copy of the command (torque mode: the run clears its own), block-uniform
+        if (kept_cmd) kept_cmd[static_cast<size_t>(d) * W + w0 + lane] = v;
     }
     if constexpr (LOCO) {
         if (wave == 1) A.rate[w0 + lane] = ft_sum_sq(tile + (kEnvTile + lane) * pitch, n, 1);
@@ -240,6 +261,92 @@ __device__ __forceinline__ void ft_write_noisy(const FloatTaskF& T, const float*
         for (int j = 0; j < 4; ++j)
             if (j < m) dst[o + j] = v[j];
     }
+}
+
+// The shaping gather of one world (mw_floatenv_shaping; lane = world, called by
+// every wave of a live lane): wave v takes the dofs, the contact links, the
+// penalised links and the active termination slots v, v + 4, ... into its
+// partial of the eight sums (float_task.hpp) and its termination hit, both
+// left in LDS for wave 0.  Per dof it reads q, qd, the kept qd of the last step
+// and -- where a torque is wanted -- the JointController's output (position
+// mode) or the kept command, clamped with the effort word the run clamped with;
+// it stores qd for the next step and the torque into the caller's row.  That
+// store is the one access here that is strided across the lanes (n words
+// apart): the tile's 64 rows are one contiguous span which the four waves
+// fill between them, and the torque of a done world must be formed here,
+// before the resets below redraw the effort limits (JOINT).  The link forces
+// are the sums of the active slots' force vectors in slot order, as the
+// observation's z force is.
+__device__ __forceinline__ void shape_gather(const FloatTaskF& T, const SimDev& S, const FreeDev& D, int n, size_t Ws,
+                                             int w, int wave, int lane, float* s_part, uint8_t* s_hit) {
+    const FloatShapeF& H = T.shape;
+    float ds[kShapeDofSums] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    float col = 0.f, stu = 0.f, exc = 0.f;
+    const float* __restrict__ tsrc = T.action_mode ? S.pid_u : H.cmd_kept;  // null: no torque is wanted
+    const float* __restrict__ eff = H.effort + static_cast<size_t>(w) * H.effort_stride;
+    float* __restrict__ tout = H.torque_out ? H.torque_out + static_cast<size_t>(w) * n : nullptr;
+    for (int d = wave; d < n; d += kEnvWaves) {
+        const size_t i = d * Ws + w;
+        const float q = S.q[i], qd = S.qd[i], prev = H.qd_prev[i];
+        float tau = 0.f;
+        if (tsrc) tau = ft_shape_tau(tsrc[i], eff[d * kWparBodyWords]);
+        if (tout) tout[d] = tau;
+        H.qd_prev[i] = qd;
+        ft_shape_dof(tau, q, qd, prev, H.env_dt, H.soft_lo[d], H.soft_hi[d], T.home_q[d], ds);
+    }
+    const uint32_t cm = D.cmask[w];
+    auto slot_force = [&](int slot, float (&f)[3]) {
+        const size_t c = (static_cast<size_t>(slot) * 7 + 3) * Ws + w;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) f[e] += D.cdata[c + e * Ws];
+    };
+    if (H.w[kShStumble] != 0.f || H.w[kShContactForce] != 0.f) {
+        for (int j = wave; j < T.n_links; j += kEnvWaves) {
+            float f[3] = {0.f, 0.f, 0.f};
+            for (uint32_t m = cm & T.link_slots[j]; m; m &= m - 1u) slot_force(__builtin_ctz(m), f);
+            ft_shape_contact(H, f[0], f[1], f[2], stu, exc);
+        }
+    }
+    if (H.w[kShCollision] != 0.f) {
+        for (int j = wave; j < H.n_pen; j += kEnvWaves) {
+            float f[3] = {0.f, 0.f, 0.f};
+            for (uint32_t m = cm & H.pen_slots[j]; m; m &= m - 1u) slot_force(__builtin_ctz(m), f);
+            col = col + ft_shape_collision(H, f[0], f[1], f[2]);
+        }
+    }
+    bool hit = false;
+    int k = 0;
+    for (uint32_t m = cm & H.term_slots; m; m &= m - 1u, ++k) {
+        if ((k & (kEnvWaves - 1)) != wave) continue;
+        float f[3] = {0.f, 0.f, 0.f};
+        slot_force(__builtin_ctz(m), f);
+        hit = hit || ft_shape_slot_hit(H, f[0], f[1], f[2]);
+    }
+    float* part = s_part + wave * kShapeSums * kEnvTile + lane;
+#pragma unroll
+    for (int e = 0; e < kShapeDofSums; ++e) part[e * kEnvTile] = ds[e];
+    part[5 * kEnvTile] = col;
+    part[6 * kEnvTile] = stu;
+    part[7 * kEnvTile] = exc;
+    s_hit[wave * kEnvTile + lane] = hit ? 1 : 0;
+}
+
+// Wave 0's half: the partials combined in wave order into the ten terms of
+// the world.  pose: the row's first seven words; standing: the command the
+// step ran under counts as standing still (LOCO only).
+__device__ __forceinline__ void shape_terms(const FloatShapeF& H, const float* pose_row, bool standing, bool diverged,
+                                            int lane, const float* s_part, float (&term)[kShapeTerms]) {
+    float sum[kShapeSums], x[kShapeTerms];
+#pragma unroll
+    for (int e = 0; e < kShapeSums; ++e) {
+        float p[kShapeLanes];
+#pragma unroll
+        for (int v = 0; v < kShapeLanes; ++v) p[v] = s_part[(v * kShapeSums + e) * kEnvTile + lane];
+        sum[e] = ft_shape_combine(p);
+    }
+    const float pose[7] = {pose_row[0], pose_row[1], pose_row[2], pose_row[3], pose_row[4], pose_row[5], pose_row[6]};
+    ft_shape_x(H, sum, pose, standing, x);
+    ft_shape_terms(H, x, diverged, term);
 }
 
 // Per world: gather the observation, reward, done, counters; where done, the
@@ -309,6 +416,16 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
     __shared__ float s_cmd[LOCO ? 3 * kEnvTile : 1];                 // the command the step ran under
     __shared__ float s_pay[LOCO ? kMaxContactLinks * kEnvTile : 1];  // touchdown payment per link
     const int NO = T.n_obs, pitch = NO | 1;
+    // shaping (block-uniform; the launcher adds kShapeLds bytes behind the tile
+    // only then, so an env without it keeps its LDS footprint): every wave's
+    // partial sums [wave][sum][lane] (the dof sums, then the link sums), the
+    // [kEnvTile][10 | 1] tiles of terms_out / ep_terms and the waves'
+    // termination hits
+    const bool shaped = __builtin_expect(T.shape.on != 0u, 0);
+    float* const s_part = tile + kEnvTile * pitch;
+    float* const s_terms = s_part + kEnvWaves * kShapeSums * kEnvTile;
+    float* const s_epterms = s_terms + kEnvTile * kShapePitch;
+    uint8_t* const s_hit = reinterpret_cast<uint8_t*>(s_epterms + kEnvTile * kShapePitch);
     const int NB = 13 + 2 * n + T.n_links;  // LOCO: the appended block starts here
     const int w0 = blockIdx.x * kEnvTile;
     const int rows = min(kEnvTile, W - w0);
@@ -378,13 +495,19 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
 #pragma unroll
                 for (int k = 0; k < 3; ++k) row[NB + 9 + k] = c[k];
             }
+            if (shaped) shape_gather(T, S, D, n, Ws, w, wave, lane, s_part, s_hit);
         }
         __syncthreads();
         if (wave == 0) {
             bool done = false;
             uint32_t episode = 0u, last = 0u;
             if (live) {
-                const bool term = ft_terminated(row[2], ft_tilt(row[4], row[5]), S.div[w] != 0, T.z_min, T.cos_tilt_max);
+                bool term = ft_terminated(row[2], ft_tilt(row[4], row[5]), S.div[w] != 0, T.z_min, T.cos_tilt_max);
+                if (shaped) {
+                    // a termination link's slot under load in the run's last substep
+#pragma unroll
+                    for (int v = 0; v < kEnvWaves; ++v) term = term || s_hit[v * kEnvTile + lane] != 0;
+                }
                 uint32_t steps = V.steps[w] + 1u;
                 done = term || (T.max_steps > 0 && steps >= static_cast<uint32_t>(T.max_steps));
                 float rew = ft_reward(T, term, row[7], asq[w], ft_sum_sq_diff(row + 13, 1, T.home_q, n));
@@ -395,6 +518,31 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
                     float pay = 0.f;
                     for (int j = 0; j < T.n_links; ++j) pay += s_pay[j * kEnvTile + lane];
                     rew = ft_loco_reward(T.loco, rew, cmd, v, om, T.loco.action_rate[w], pay);
+                }
+                if (shaped) {
+                    const FloatShapeF& H = T.shape;
+                    const bool diverged = S.div[w] != 0;
+                    bool standing = false;
+                    if constexpr (LOCO) standing = ft_shape_standing(s_cmd[lane], s_cmd[kEnvTile + lane], T.loco.cmd_min);
+                    float term_k[kShapeTerms], acc_t[kShapeTerms], ep_t[kShapeTerms];
+                    shape_terms(H, row, standing, diverged, lane, s_part, term_k);
+                    rew = ft_shape_reward(rew, term_k);
+                    // the episode's running sums; where done, out as the finished episode's and zeroed
+                    float acc_r = H.acc_return[w], ep_r = 0.f;
+                    int32_t acc_l = H.acc_length[w], ep_l = 0;
+#pragma unroll
+                    for (int k = 0; k < kShapeTerms; ++k) acc_t[k] = H.acc_terms[k * Ws + w];
+                    const bool finished = ft_shape_stats(rew, term_k, diverged, done, acc_r, acc_l, acc_t, ep_r, ep_l, ep_t);
+                    H.acc_return[w] = acc_r;
+                    H.acc_length[w] = acc_l;
+#pragma unroll
+                    for (int k = 0; k < kShapeTerms; ++k) {
+                        H.acc_terms[k * Ws + w] = acc_t[k];
+                        s_terms[lane * kShapePitch + k] = term_k[k];
+                        if (finished) s_epterms[lane * kShapePitch + k] = ep_t[k];
+                    }
+                    if (finished && H.ep_return) H.ep_return[w] = ep_r;
+                    if (finished && H.ep_length) H.ep_length[w] = ep_l;
                 }
                 reward[w] = rew;
                 done_out[w] = done ? 1 : 0;
@@ -423,6 +571,17 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
                     for (int k = lane; k < NO; k += 64)
                         term_obs[static_cast<size_t>(w0 + r) * NO + k] = tile[r * pitch + k];
         }
+        if (shaped) {
+            // the tiles of the terms: [rows, 10] is one contiguous span of either output
+            float* __restrict__ terms_out = T.shape.terms_out;
+            float* __restrict__ ep_terms = T.shape.ep_terms;
+            for (int i = threadIdx.x; i < rows * kShapeTerms; i += kEnvThreads) {
+                const int r = i / kShapeTerms, k = i - r * kShapeTerms;
+                const size_t o = static_cast<size_t>(w0) * kShapeTerms + i;
+                if (terms_out) terms_out[o] = s_terms[r * kShapePitch + k];
+                if (ep_terms && s_done[r]) ep_terms[o] = s_epterms[r * kShapePitch + k];
+            }
+        }
         __syncthreads();
     } else {
         if (wave == 0) {
@@ -432,6 +591,13 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
             if (live) {
                 V.episode[w] = 0u;
                 V.steps[w] = 0u;
+                if (shaped) {
+                    // the running sums start over; the finished episodes' buffers stay
+                    T.shape.acc_return[w] = 0.f;
+                    T.shape.acc_length[w] = 0;
+#pragma unroll
+                    for (int k = 0; k < kShapeTerms; ++k) T.shape.acc_terms[k * Ws + w] = 0.f;
+                }
             }
         }
         __syncthreads();
@@ -603,6 +769,10 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
             row[13 + 2 * n + j] = 0.f;
             if constexpr (LOCO) T.loco.air_steps[j * Ws + w] = 0u;
         }
+        if (shaped) {
+            // joint_acc of an episode's first step is taken from rest (the wave that wrote the word)
+            for (int d = wave; d < n; d += kEnvWaves) T.shape.qd_prev[d * Ws + w] = 0.f;
+        }
         if constexpr (LOCO) {
             for (int d = wave; d < n; d += kEnvWaves) {
                 row[NB + 12 + d] = 0.f;
@@ -659,7 +829,7 @@ static void launch_action(const FloatTaskF& T, const float* actions, float* out,
         for (int d = 0; d < kMaxBodies; ++d) L.home_q[d] = T.home_q[d];
     }
     hipLaunchKernelGGL((dev::float_env_action_kernel<LOCO, DELAY>), grid, block, lds, st, actions, out, asq, div, ndiv, n,
-                       W, A, L);
+                       W, A, L, T.action_mode == 0 ? T.shape.cmd_kept : nullptr);
 }
 
 hipError_t launch_float_env_action(const FloatTaskF& T, const float* actions, float* out, float* asq, uint8_t* div,
@@ -684,11 +854,13 @@ constexpr auto kPostKernels = post_kernels(std::make_index_sequence<32>{});
 hipError_t launch_float_env_post(const ChainF* P, const FloatTaskF& T, const SimDev& S, const FreeDev& D,
                                  const VecDev& V, const float* asq, float* obs, float* reward, uint8_t* done,
                                  float* term_obs, int n, int W, int reset_all, hipStream_t st) {
-    const size_t lds = static_cast<size_t>(dev::kEnvTile) * (T.n_obs | 1) * sizeof(float);
+    const size_t lds = static_cast<size_t>(dev::kEnvTile) * (T.n_obs | 1) * sizeof(float) +
+                       (T.shape.on ? dev::kShapeLds : 0);
     const dim3 grid((W + dev::kEnvTile - 1) / dev::kEnvTile), block(dev::kEnvThreads);
     // The locomotion rows are 25 + 3 n + n_links words: at most (48 dofs, 8
-    // links) 64 x 177 words = 45 KB, with the kernel's 3.6 KB of static LDS
-    // still inside the 64 KB a block gets without asking for more.
+    // links) 64 x 177 words = 45,312 B, with the 14,080 B of the shaping branch
+    // (partials, term tiles, hits) and the kernel's 3,648 B of static LDS still
+    // inside the 65,536 B a block gets without asking for more.
     const bool rand = T.rand.friction_hi > 0.f, push = T.rand.push_interval > 0u, loco = T.loco.on != 0u;
     const bool inert = T.inertia.wpar != nullptr, joint = T.joints.wpar != nullptr;
     hipLaunchKernelGGL(kPostKernels[rand | push << 1 | loco << 2 | inert << 3 | joint << 4], grid, block, lds, st, P, T,

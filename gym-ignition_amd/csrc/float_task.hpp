@@ -14,13 +14,19 @@
 // air-time counter, the extra reward terms), built by
 // tests/host_float_loco/harness.cpp, and that of the observation noise and the
 // action latency (mw_floatenv_noise: the noise unit, the noisy word, the delay
-// draw and the ring's slots), built by tests/host_float_noise/harness.cpp.
+// draw and the ring's slots), built by tests/host_float_noise/harness.cpp, and
+// that of the shaping rewards, the contact termination and the episode
+// statistics (mw_floatenv_shaping: the ten terms, the slot predicate, the
+// accumulator step), built by tests/host_float_shape/harness.cpp.
 #pragma once
 
 #ifdef MW_HOST_TEST
 #include <cmath>
 #ifndef __device__
 #define __device__
+#endif
+#ifndef __host__
+#define __host__
 #endif
 #ifndef __forceinline__
 #define __forceinline__ inline
@@ -123,6 +129,54 @@ struct FloatNoiseF {
     int32_t* delay_out;        // [W] the same words (caller's, may be null)
 };
 
+// Shaping rewards, contact termination and episode statistics of the
+// floating-base env (mw_floatenv_shaping), off when `on` is zero.  Column k of
+// a world's row of terms is -w[k] x_k of the step, x_k as listed; a weight of
+// zero skips the term, which then reports 0.
+constexpr int kShapeTerms = 10;
+enum ShapeTerm : int {
+    kShTorque = 0,     // sum_d tau_d^2
+    kShPower,          // sum_d |tau_d qd_d|
+    kShJointAcc,       // sum_d ((qd_d - qd_prev_d) / env_dt)^2
+    kShOrientation,    // g_x^2 + g_y^2 of the projected gravity
+    kShBaseHeight,     // (z - base_height_target)^2
+    kShJointLimits,    // sum_d max(0, lo_d - q_d) + max(0, q_d - hi_d), lo / hi the soft limits
+    kShCollision,      // penalised links whose contact force norm exceeds collision_force_min
+    kShStumble,        // contact links with hypot(f_x, f_y) > stumble_ratio |f_z| and |f_z| > 0
+    kShContactForce,   // sum over the contact links of max(0, |f| - max_contact_force)
+    kShStandStill,     // sum_d |q_d - home_q_d| under a command with v_x^2 + v_y^2 <= cmd_min^2
+};
+// A sum over dofs or links is taken in kShapeLanes partial sums -- item i goes
+// to partial i % kShapeLanes, each partial in index order -- which are then
+// added in order: ((p_0 + p_1) + p_2) + p_3.  The post kernel's four waves
+// each own one partial; a host build runs the same order.
+constexpr int kShapeLanes = 4;
+constexpr int kShapeDofSums = 5;   // torque, power, joint_acc, joint_limits, stand_still
+constexpr int kShapeLinkSums = 3;  // collision, stumble, contact_force
+constexpr int kShapeSums = kShapeDofSums + kShapeLinkSums;  // the dof sums, then the link sums
+struct FloatShapeF {
+    uint32_t on;
+    uint32_t term_slots;           // union of the termination links' contact slots (FreeDev::cmask bits)
+    float w[kShapeTerms];          // >= 0
+    float base_height_target, collision_force_min, stumble_ratio, max_contact_force, termination_force;
+    float env_dt;                  // steps_per_run * step_size (s)
+    int32_t n_pen;                 // penalised links
+    uint32_t pen_slots[kMaxContactLinks];  // contact slots of every penalised link
+    float soft_lo[kMaxBodies], soft_hi[kMaxBodies];  // -/+ kFtUnbounded for a joint without finite limits
+    const float* effort;           // the effort word of body 0: the shared ChainF's, or world 0's record (RunArgs::wpar)
+    int32_t effort_stride;         // words between two worlds' records, 0 with the shared model
+    float* qd_prev;                // [n][W] qd after the last step, zeros after a reset (the env's own)
+    float* cmd_kept;               // [n][W] torque mode: the command the action launch stored (the env's own, may be null)
+    float* terms_out;              // [W, 10] the step's terms (caller's, may be null)
+    float* torque_out;             // [W, n] the torque the terms used (caller's, may be null)
+    float* acc_return;             // [W] running sums of the current episode (the env's own)
+    int32_t* acc_length;           // [W]
+    float* acc_terms;              // [10][W]
+    float* ep_return;              // [W] the last finished episode of every world (caller's, each may be null)
+    int32_t* ep_length;            // [W]
+    float* ep_terms;               // [W, 10]
+};
+
 // Task description of the floating-base env (kernel argument, by value).
 struct FloatTaskF {
     int32_t action_mode;     // 0 torque (SimDev::cmd), 1 position (SimDev::ptgt)
@@ -142,6 +196,7 @@ struct FloatTaskF {
     FloatInertiaF inertia;
     FloatJointF joints;
     FloatNoiseF noise;
+    FloatShapeF shape;
 };
 
 namespace dev {
@@ -301,8 +356,6 @@ __device__ __forceinline__ void ft_joint_words(const float (&nom)[3], const floa
 // Philox block of joint d's draws (words 0, 1, 2: damping, friction, effort)
 __device__ __forceinline__ uint32_t ft_joint_block(int d) { return kFtJointBlock | static_cast<uint32_t>(d); }
 
-#undef MW_FT_NO_CONTRACT
-
 // Philox block of link k's scale (k = 0 the base, 1 + i body i); its word is k % 4
 __device__ __forceinline__ uint32_t ft_scale_block(int k) { return kFtScaleBlock | static_cast<uint32_t>(k >> 2); }
 
@@ -358,6 +411,185 @@ __device__ __forceinline__ float ft_loco_reward(const FloatLocoF& L, float base_
     if (cmd[0] * cmd[0] + cmd[1] * cmd[1] > L.cmd_min * L.cmd_min) r += L.w_air_time * air_pay;
     return r;
 }
+
+// ---- shaping rewards, contact termination, episode statistics (FloatShapeF) ----
+// Every product and sum below has a defined rounding, as the inertial words
+// above: a fused operation is an explicit fmaf, every other one is rounded on
+// its own (contraction off), sums run in the order written.  A term is then
+// the same bits from hipcc and from a host compiler.
+
+// The soft limits of a joint: centre -/+ soft_limit * half-range; a joint
+// without finite limits (either word at kFtUnbounded) gets -/+ kFtUnbounded
+// and never contributes.  mw_floatenv_shaping runs it on the host.
+__host__ __device__ __forceinline__ void ft_soft_limits(float lower, float upper, float soft, float& lo, float& hi) {
+    MW_FT_NO_CONTRACT
+    lo = -kFtUnbounded;
+    hi = kFtUnbounded;
+    if (!(lower > -kFtUnbounded) || !(upper < kFtUnbounded)) return;
+    const float sum = lower + upper, dif = upper - lower;
+    const float c = 0.5f * sum, h = 0.5f * dif;
+    const float sh = soft * h;
+    lo = c - sh;
+    hi = c + sh;
+}
+
+// The torque the run's substeps used: dof_force's clamp (kernels.hip) of the
+// JointController's last output (position mode) or of the stored command.
+__device__ __forceinline__ float ft_shape_tau(float u, float effort) { return fminf(fmaxf(u, -effort), effort); }
+
+// One dof into the five dof sums of its partial: torque (one rounding), power
+// (two), joint_acc (three), joint_limits (at most three), stand_still (two).
+__device__ __forceinline__ void ft_shape_dof(float tau, float q, float qd, float qd_prev, float env_dt, float lo,
+                                             float hi, float home, float (&acc)[kShapeDofSums]) {
+    MW_FT_NO_CONTRACT
+    acc[0] = fmaf(tau, tau, acc[0]);
+    const float p = tau * qd;
+    acc[1] = acc[1] + fabsf(p);
+    const float dv = qd - qd_prev;
+    const float a = dv / env_dt;
+    acc[2] = fmaf(a, a, acc[2]);
+    const float below = lo - q, above = q - hi;
+    const float out = fmaxf(0.f, below) + fmaxf(0.f, above);
+    acc[3] = acc[3] + out;
+    const float e = q - home;
+    acc[4] = acc[4] + fabsf(e);
+}
+
+// |f| of a force vector: sqrt(fz^2 + (fy^2 + fx^2)), four roundings
+__device__ __forceinline__ float ft_force_norm(float fx, float fy, float fz) {
+    MW_FT_NO_CONTRACT
+    const float xx = fx * fx;
+    const float xy = fmaf(fy, fy, xx);
+    return sqrtf(fmaf(fz, fz, xy));
+}
+
+// A contact slot of a termination link ends the episode when its force norm
+// exceeds termination_force (the slot is active in cmask: the caller's test).
+__device__ __forceinline__ bool ft_shape_slot_hit(const FloatShapeF& H, float fx, float fy, float fz) {
+    return ft_force_norm(fx, fy, fz) > H.termination_force;
+}
+
+// A penalised link with the summed force f of its active slots: 1 where |f| > collision_force_min
+__device__ __forceinline__ float ft_shape_collision(const FloatShapeF& H, float fx, float fy, float fz) {
+    return ft_force_norm(fx, fy, fz) > H.collision_force_min ? 1.f : 0.f;
+}
+
+// A contact link with the summed force f of its active slots into the stumble
+// count and the excess-force sum of its partial.
+__device__ __forceinline__ void ft_shape_contact(const FloatShapeF& H, float fx, float fy, float fz, float& stumble,
+                                                 float& excess) {
+    MW_FT_NO_CONTRACT
+    const float xx = fx * fx;
+    const float hxy = sqrtf(fmaf(fy, fy, xx));
+    const float az = fabsf(fz);
+    const float lim = H.stumble_ratio * az;
+    stumble = stumble + ((az > 0.f && hxy > lim) ? 1.f : 0.f);
+    const float over = ft_force_norm(fx, fy, fz) - H.max_contact_force;
+    excess = excess + fmaxf(0.f, over);
+}
+
+// The partials of one sum added in order
+__device__ __forceinline__ float ft_shape_combine(const float (&p)[kShapeLanes]) {
+    MW_FT_NO_CONTRACT
+    float s = p[0];
+#pragma unroll
+    for (int v = 1; v < kShapeLanes; ++v) s = s + p[v];
+    return s;
+}
+
+// g_x^2 + g_y^2 of the projected gravity (ft_projected_gravity's first two
+// words, here with defined rounding): g_x = -2 (qx qz - qw qy), g_y = -2 (qy qz
+// + qw qx); the doublings are exact, six roundings in all.
+__device__ __forceinline__ float ft_shape_orientation(float qw, float qx, float qy, float qz) {
+    MW_FT_NO_CONTRACT
+    const float xz = qx * qz, yz = qy * qz;
+    const float hx = fmaf(-qw, qy, xz), hy = fmaf(qw, qx, yz);
+    const float gx = -(2.f * hx), gy = -(2.f * hy);
+    const float xx = gx * gx;
+    return fmaf(gy, gy, xx);
+}
+
+// (z - target)^2, two roundings
+__device__ __forceinline__ float ft_shape_height(float z, float target) {
+    MW_FT_NO_CONTRACT
+    const float e = z - target;
+    return e * e;
+}
+
+// stand_still counts under a command with v_x^2 + v_y^2 <= cmd_min^2
+__device__ __forceinline__ bool ft_shape_standing(float cx, float cy, float cmd_min) {
+    MW_FT_NO_CONTRACT
+    const float xx = cx * cx;
+    const float c2 = fmaf(cy, cy, xx), m2 = cmd_min * cmd_min;
+    return c2 <= m2;
+}
+
+// The ten x of a world from its eight combined sums (kShapeDofSums, then
+// kShapeLinkSums), the base's pose words (x y z qw qx qy qz) and whether the
+// command counts as standing still.
+__device__ __forceinline__ void ft_shape_x(const FloatShapeF& H, const float (&sum)[kShapeSums], const float (&pose)[7],
+                                           bool standing, float (&x)[kShapeTerms]) {
+    x[kShTorque] = sum[0];
+    x[kShPower] = sum[1];
+    x[kShJointAcc] = sum[2];
+    x[kShOrientation] = ft_shape_orientation(pose[3], pose[4], pose[5], pose[6]);
+    x[kShBaseHeight] = ft_shape_height(pose[2], H.base_height_target);
+    x[kShJointLimits] = sum[3];
+    x[kShCollision] = sum[5];
+    x[kShStumble] = sum[6];
+    x[kShContactForce] = sum[7];
+    x[kShStandStill] = standing ? sum[4] : 0.f;
+}
+
+// The ten signed terms from the ten x: -(w x), one rounding; 0 where the
+// weight is zero or the world diverged (its state is not finite).
+__device__ __forceinline__ void ft_shape_terms(const FloatShapeF& H, const float (&x)[kShapeTerms], bool diverged,
+                                               float (&term)[kShapeTerms]) {
+    MW_FT_NO_CONTRACT
+#pragma unroll
+    for (int k = 0; k < kShapeTerms; ++k) {
+        const float wx = H.w[k] * x[k];
+        term[k] = (H.w[k] != 0.f && !diverged) ? -wx : 0.f;
+    }
+}
+
+// reward = r_existing + term[0] + ... + term[9], in that order
+__device__ __forceinline__ float ft_shape_reward(float r_existing, const float (&term)[kShapeTerms]) {
+    MW_FT_NO_CONTRACT
+    float r = r_existing;
+#pragma unroll
+    for (int k = 0; k < kShapeTerms; ++k) r = r + term[k];
+    return r;
+}
+
+// One step of a world's episode statistics: the running sums take the step
+// (nothing from a diverged world); where done they are copied out as the
+// finished episode (finished = true, ep_* filled) and zeroed.
+__device__ __forceinline__ bool ft_shape_stats(float reward, const float (&term)[kShapeTerms], bool diverged, bool done,
+                                               float& acc_return, int32_t& acc_length,
+                                               float (&acc_terms)[kShapeTerms], float& ep_return, int32_t& ep_length,
+                                               float (&ep_terms)[kShapeTerms]) {
+    MW_FT_NO_CONTRACT
+    if (!diverged) {
+        acc_return = acc_return + reward;
+        acc_length += 1;
+#pragma unroll
+        for (int k = 0; k < kShapeTerms; ++k) acc_terms[k] = acc_terms[k] + term[k];
+    }
+    if (!done) return false;
+    ep_return = acc_return;
+    ep_length = acc_length;
+    acc_return = 0.f;
+    acc_length = 0;
+#pragma unroll
+    for (int k = 0; k < kShapeTerms; ++k) {
+        ep_terms[k] = acc_terms[k];
+        acc_terms[k] = 0.f;
+    }
+    return true;
+}
+
+#undef MW_FT_NO_CONTRACT
 
 }  // namespace dev
 }  // namespace mw

@@ -46,6 +46,14 @@ struct mw_vecenv {
     mw::dev_ptr<float[]> d_noise_amp;
     mw::dev_ptr<float[]> d_action_ring;
     mw::dev_ptr<int32_t[]> d_action_delay;
+    // shaping rewards and episode statistics (mw_floatenv_shaping): qd of the
+    // last step [n][W], in torque mode the command the action launch stored
+    // [n][W], and the running sums of the current episodes: return [W] then
+    // terms [10][W] in one buffer, length [W]
+    mw::dev_ptr<float[]> d_shape_qd;
+    mw::dev_ptr<float[]> d_shape_cmd;
+    mw::dev_ptr<float[]> d_shape_sums;
+    mw::dev_ptr<int32_t[]> d_shape_length;
 
     // the env's work (on its simulator's stream) drains before the members release their buffers
     ~mw_vecenv() { if (sim && sim->stream) (void)hipStreamSynchronize(sim->stream); }
@@ -525,6 +533,142 @@ int mw_floatenv_noise(mw_vecenv* e, const mw_float_noise_config* cfg, const floa
     return MW_OK;
 }
 
+// Shaping rewards, contact termination and episode statistics of a
+// floating-base env: one more runtime branch of the post launch
+// (float_env_kernel.hip: shape_gather, shape_terms), and in torque mode a
+// nullable argument of the action launch.
+static_assert(mw::kShapeTerms == MW_FLOAT_SHAPE_TERMS, "the term count of float_task.hpp is the ABI's");
+int mw_floatenv_shaping(mw_vecenv* e, const mw_float_shape_config* cfg, float* terms_out, float* torque_out,
+                        float* ep_return, int32_t* ep_length, float* ep_terms) {
+    if (!e || !cfg) return fail(MW_EINVAL, "null argument");
+    if (!e->floatenv) return fail(MW_ESTATE, "mw_floatenv_shaping needs an env made by mw_floatenv_create");
+    if (e->was_reset) return fail(MW_ESTATE, "mw_floatenv_shaping must be called before the first mw_vecenv_reset");
+    mw_sim* s = e->sim;
+    mw::FloatTaskF& T = e->ftask;
+    const int n = s->n;
+    const float scalars[] = {cfg->base_height_target, cfg->soft_limit,        cfg->collision_force_min,
+                             cfg->stumble_ratio,      cfg->max_contact_force, cfg->termination_force};
+    bool any = cfg->n_penalised_links != 0 || cfg->n_termination_links != 0;
+    for (int k = 0; k < mw::kShapeTerms; ++k) {
+        if (!std::isfinite(cfg->weights[k])) return fail(MW_EINVAL, "every field of mw_float_shape_config must be finite");
+        if (cfg->weights[k] < 0.f) return fail(MW_EINVAL, "the weights of mw_float_shape_config must be >= 0");
+        any = any || cfg->weights[k] != 0.f;
+    }
+    for (float f : scalars) {
+        if (!std::isfinite(f)) return fail(MW_EINVAL, "every field of mw_float_shape_config must be finite");
+        any = any || f != 0.f;
+    }
+    if (cfg->n_penalised_links < 0 || cfg->n_penalised_links > mw::kMaxContactLinks)
+        return fail(MW_EINVAL, "n_penalised_links must be in [0, " + std::to_string(mw::kMaxContactLinks) + "]");
+    if (cfg->n_termination_links < 0) return fail(MW_EINVAL, "n_termination_links must be >= 0");
+    if ((cfg->n_penalised_links > 0 && !cfg->penalised_links) || (cfg->n_termination_links > 0 && !cfg->termination_links))
+        return fail(MW_EINVAL, "a link list of mw_float_shape_config is null");
+    if (!any) {  // everything off: the env as it was made
+        T.shape = mw::FloatShapeF{};
+        e->d_shape_qd.reset();
+        e->d_shape_cmd.reset();
+        e->d_shape_sums.reset();
+        e->d_shape_length.reset();
+        return MW_OK;
+    }
+    if (!(cfg->soft_limit > 0.f && cfg->soft_limit <= 1.f)) return fail(MW_EINVAL, "soft_limit must be in (0, 1]");
+    if (cfg->collision_force_min < 0.f || cfg->stumble_ratio < 0.f || cfg->max_contact_force < 0.f ||
+        cfg->termination_force < 0.f)
+        return fail(MW_EINVAL, "collision_force_min, stumble_ratio, max_contact_force and termination_force must be >= 0");
+    if (cfg->weights[mw::kShStandStill] != 0.f && !T.loco.on)
+        return fail(MW_ESTATE, "the stand_still term needs the locomotion task: call mw_floatenv_locomotion first");
+    if (cfg->weights[mw::kShCollision] != 0.f && cfg->n_penalised_links == 0)
+        return fail(MW_EINVAL, "the collision term needs penalised links");
+    if ((cfg->weights[mw::kShStumble] != 0.f || cfg->weights[mw::kShContactForce] != 0.f) && T.n_links == 0)
+        return fail(MW_EINVAL, "the stumble and contact_force terms need contact links (mw_float_task_config)");
+    // the contact slots of a link among the 32 of the wave kernel's mask (as
+    // mw_floatenv_create finds a contact link's); a link without one could never fire
+    auto slots_of = [&](int32_t link, const char* what, uint32_t& slots) {
+        slots = 0u;
+        if (link < -1 || link >= n)
+            return fail(MW_EINVAL, std::string(what) + " link " + std::to_string(link) + " out of range [-1, " +
+                                       std::to_string(n) + ")");
+        for (int slot = 0; slot < s->n_slots && slot < 32; ++slot)
+            if (s->slot_body[slot] == link) slots |= 1u << slot;
+        if (!slots)
+            return fail(MW_EINVAL, std::string(what) + " link " + std::to_string(link) +
+                                       " owns no contact slot among the 32 of the contact mask (no collision shape?)");
+        return MW_OK;
+    };
+    uint32_t pen_slots[mw::kMaxContactLinks] = {}, term_slots = 0u;
+    for (int j = 0; j < cfg->n_penalised_links; ++j)
+        if (int rc = slots_of(cfg->penalised_links[j], "penalised", pen_slots[j])) return rc;
+    for (int j = 0; j < cfg->n_termination_links; ++j) {
+        uint32_t m;
+        if (int rc = slots_of(cfg->termination_links[j], "termination", m)) return rc;
+        term_slots |= m;
+    }
+    const size_t W = static_cast<size_t>(s->W), nw = static_cast<size_t>(n) * W;
+    const bool keep_cmd = T.action_mode == MW_FLOAT_ACTION_TORQUE &&
+                          (cfg->weights[mw::kShTorque] != 0.f || cfg->weights[mw::kShPower] != 0.f || torque_out);
+    MW_HIP(hipSetDevice(s->cfg.device));
+    // the allocations first: a failed call leaves the env as it was
+    mw::dev_ptr<float[]> qd, cmd, sums;
+    mw::dev_ptr<int32_t[]> len;
+    const size_t sum_words = (1 + mw::kShapeTerms) * W;
+    MW_HIP(mw::dev_alloc(qd, nw * sizeof(float)));
+    if (keep_cmd) MW_HIP(mw::dev_alloc(cmd, nw * sizeof(float)));
+    MW_HIP(mw::dev_alloc(sums, sum_words * sizeof(float)));
+    MW_HIP(mw::dev_alloc(len, W * sizeof(int32_t)));
+    MW_HIP(hipMemsetAsync(qd.get(), 0, nw * sizeof(float), s->stream));
+    if (keep_cmd) MW_HIP(hipMemsetAsync(cmd.get(), 0, nw * sizeof(float), s->stream));
+    MW_HIP(hipMemsetAsync(sums.get(), 0, sum_words * sizeof(float), s->stream));
+    MW_HIP(hipMemsetAsync(len.get(), 0, W * sizeof(int32_t), s->stream));
+    e->d_shape_qd = std::move(qd);
+    e->d_shape_cmd = std::move(cmd);
+    e->d_shape_sums = std::move(sums);
+    e->d_shape_length = std::move(len);
+    mw::FloatShapeF& H = T.shape;
+    H = mw::FloatShapeF{};
+    H.on = 1u;
+    H.term_slots = term_slots;
+    for (int k = 0; k < mw::kShapeTerms; ++k) H.w[k] = cfg->weights[k];
+    H.base_height_target = cfg->base_height_target;
+    H.collision_force_min = cfg->collision_force_min;
+    H.stumble_ratio = cfg->stumble_ratio;
+    H.max_contact_force = cfg->max_contact_force;
+    H.termination_force = cfg->termination_force;
+    H.env_dt = static_cast<float>(s->cfg.steps_per_run * s->cfg.step_size);
+    H.n_pen = cfg->n_penalised_links;
+    for (int j = 0; j < cfg->n_penalised_links; ++j) H.pen_slots[j] = pen_slots[j];
+    for (int d = 0; d < mw::kMaxBodies; ++d) {
+        H.soft_lo[d] = -mw::kFtUnbounded;
+        H.soft_hi[d] = mw::kFtUnbounded;
+        if (d < n) mw::dev::ft_soft_limits(s->h_params.b[d].lower, s->h_params.b[d].upper, cfg->soft_limit, H.soft_lo[d], H.soft_hi[d]);
+    }
+    H.qd_prev = e->d_shape_qd.get();
+    H.cmd_kept = e->d_shape_cmd.get();
+    H.terms_out = terms_out;
+    H.torque_out = torque_out;
+    H.acc_return = e->d_shape_sums.get();
+    H.acc_terms = e->d_shape_sums.get() + W;
+    H.acc_length = e->d_shape_length.get();
+    H.ep_return = ep_return;
+    H.ep_length = ep_length;
+    H.ep_terms = ep_terms;
+    return MW_OK;
+}
+
+// The effort word the next run clamps with: the world's record where the
+// simulator has per-world link parameters (the pointer and stride RunArgs::wpar
+// gets), else the shared model's.
+static void shaping_effort(mw_vecenv* e) {
+    mw_sim* s = e->sim;
+    mw::FloatShapeF& H = e->ftask.shape;
+    if (s->d_wpar) {
+        H.effort = s->d_wpar.get() + mw::kWparBody0 + mw::kBodyEffort;
+        H.effort_stride = s->wpar_stride;
+    } else {
+        H.effort = reinterpret_cast<const float*>(s->d_params.get()) + mw::kWparHeadWords + mw::kBodyEffort;
+        H.effort_stride = 0;
+    }
+}
+
 static int floatenv_reset(mw_vecenv* e, float* obs) {
     mw_sim* s = e->sim;
     e->was_reset = true;
@@ -542,6 +686,7 @@ static int floatenv_step(mw_vecenv* e, const void* a, float* o, float* r, uint8_
                                        e->d_asq.get(), s->dev.div, s->dev.ndiv, s->n, s->W, s->stream));
     if (pos) s->ptgt_stale = true;  // the host mirror of the targets re-reads the device copy
     if (int rc = run_impl(s, 0, false)) return rc;
+    if (e->ftask.shape.on) shaping_effort(e);
     MW_HIP(mw::launch_float_env_post(s->d_params.get(), e->ftask, s->dev, s->fdev, e->dev, e->d_asq.get(), o, r, d, to,
                                      s->n, s->W, 0, s->stream));
     return MW_OK;

@@ -41,6 +41,15 @@ policy side of sim-to-real randomisation inside the same three launches:
 per-word uniform noise on ``obs`` and ``terminal_obs`` with the clean rows kept
 beside them (``env.clean_obs``), and a per-episode latency of up to 8 control
 steps between an action and the command the simulator receives.
+
+``reward_terms=``, ``termination_links=`` and ``penalised_links=``
+(``mw_floatenv_shaping``) add, again inside the same three launches, the
+regularisers that keep a learned gait physical -- joint torque, mechanical
+power, joint acceleration, base orientation and height, joint limits,
+collisions of non-foot links, stumbling, excessive foot forces, standing still
+-- as ten signed reward columns (``env.reward_terms``), a termination on
+contact of chosen links, and per-episode statistics of the finished episodes
+(``env.episode_return``, ``env.episode_length``, ``env.episode_terms``).
 """
 
 from __future__ import annotations
@@ -61,6 +70,9 @@ from .sim import Simulator
 ACTION_MODES = {"torque": N.FLOAT_ACTION_TORQUE, "position": N.FLOAT_ACTION_POSITION}
 TASKS = ("forward", "locomotion")
 MAX_CONTACT_LINKS = 8
+# the columns of env.reward_terms, in order (mw_float_shape_config::weights)
+REWARD_TERMS = ("torque", "power", "joint_acc", "orientation", "base_height", "joint_limits", "collision", "stumble",
+                "contact_force", "stand_still")
 
 
 def _torch():
@@ -108,7 +120,11 @@ class FloatVecEnv:
                  track_sigma: float = 0.25, w_lin_z: float = 0.0, w_ang_xy: float = 0.0,
                  w_action_rate: float = 0.0, w_air_time: float = 0.0, air_time_target: float = 0.0,
                  contact_force_min: float = 1.0,
-                 obs_noise=None, action_delay_range: Optional[Sequence[int]] = None):
+                 obs_noise=None, action_delay_range: Optional[Sequence[int]] = None,
+                 reward_terms: Optional[Mapping] = None, termination_links: Optional[Sequence] = None,
+                 termination_force: float = 1.0, penalised_links: Sequence = (), collision_force_min: float = 0.1,
+                 base_height_target: Optional[float] = None, soft_limit: float = 0.9, stumble_ratio: float = 5.0,
+                 max_contact_force: float = 100.0):
         """``model``: a shipped model's name or a URDF / SDF file.  ``home_q``
         (one value per dof) and ``home_base`` (x y z qw qx qy qz) are the reset
         state; ``pid_gains`` per dof ``(p, i, d)`` or the eight values of
@@ -194,7 +210,40 @@ class FloatVecEnv:
         the last-action words stay on the action just given.
         ``env.action_delay`` ``[n_worlds]`` int32 (also
         ``info["action_delay"]``) holds the current delays.  Each attribute is
-        ``None`` with its feature off."""
+        ``None`` with its feature off.
+
+        Shaping rewards, contact termination and episode statistics
+        (``mw_floatenv_shaping``), on when ``reward_terms``,
+        ``termination_links`` or ``penalised_links`` is given.  ``reward_terms``
+        maps term names to weights >= 0; a step's reward gains ``-weight * x``
+        per term, in this order: ``torque`` (sum tau^2), ``power`` (sum |tau
+        qd|), ``joint_acc`` (sum of squared finite-difference joint
+        accelerations), ``orientation`` (g_x^2 + g_y^2 of the projected
+        gravity), ``base_height`` ((z - ``base_height_target``)^2; default: the
+        home height), ``joint_limits`` (distance beyond ``soft_limit`` times
+        the half-range around the centre of the position limits),
+        ``collision`` (number of ``penalised_links`` pressed with more than
+        ``collision_force_min`` N), ``stumble`` (contact links whose horizontal
+        force exceeds ``stumble_ratio`` times the vertical one),
+        ``contact_force`` (force of the contact links above
+        ``max_contact_force`` N) and ``stand_still`` (sum |q - home_q| under a
+        command slower than ``cmd_min``; needs ``task="locomotion"``).  tau is
+        the torque the simulator applied, clamped with the world's own effort
+        limit.  ``termination_links``: the episode ends -- terminated, without
+        the alive bonus -- when a contact point of one of these links carries
+        more than ``termination_force`` N.  Contacts are those of the last
+        physics step of a control step: with ``steps_per_run`` > 1 a touch that
+        ends earlier within the step is not seen.  Link names resolve as
+        ``contact_links`` do; a link without a collision shape is refused,
+        since it could never fire.  ``env.reward_term_names`` holds the ten
+        names, ``env.reward_terms`` ``[n_worlds, 10]`` the step's signed terms,
+        ``env.torques`` ``[n_worlds, n]`` the torque they used, and
+        ``env.episode_return`` ``[n_worlds]``, ``env.episode_length``
+        ``[n_worlds]`` int32 and ``env.episode_terms`` ``[n_worlds, 10]`` the
+        return, length and term sums of the last finished episode of each
+        world, valid where that world has been ``done`` (``reset()`` starts the
+        running sums over and leaves these three alone).  All are mirrored in ``info``
+        under the same names and are ``None`` with the feature off."""
         torch = _torch()
         if action_mode not in ACTION_MODES:
             raise ValueError(f"unknown action_mode {action_mode!r}; known: {sorted(ACTION_MODES)}")
@@ -363,6 +412,39 @@ class FloatVecEnv:
                 h, ctypes.byref(nc), None if amp is None else amp.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                 ptr(self.clean_obs), ptr(self.clean_terminal_obs), ptr(self.action_delay)), "mw_floatenv_noise")
 
+        self.reward_term_names = self.reward_terms = self.torques = None
+        self.episode_return = self.episode_length = self.episode_terms = None
+        self.termination_links = self.penalised_links = None
+        if reward_terms or termination_links or penalised_links:
+            weights = np.zeros(N.FLOAT_SHAPE_TERMS, np.float32)
+            for name, value in (reward_terms or {}).items():
+                if name not in REWARD_TERMS:
+                    raise ValueError(f"reward_terms: unknown term {name!r}; known: {list(REWARD_TERMS)}")
+                weights[REWARD_TERMS.index(name)] = value
+            self.termination_links = self._resolve_links(model_file, termination_links or (), limit=None)
+            self.penalised_links = self._resolve_links(model_file, penalised_links or ())
+            term = np.ascontiguousarray(self.termination_links, dtype=np.int32)
+            pen = np.ascontiguousarray(self.penalised_links, dtype=np.int32)
+            ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if len(a) else None
+            self.reward_term_names = REWARD_TERMS
+            self.reward_terms = torch.zeros((n_worlds, N.FLOAT_SHAPE_TERMS), **f32)
+            self.torques = torch.zeros((n_worlds, n), **f32)
+            self.episode_return = torch.zeros((n_worlds,), **f32)
+            self.episode_length = torch.zeros((n_worlds,), dtype=torch.int32, device=self.device)
+            self.episode_terms = torch.zeros((n_worlds, N.FLOAT_SHAPE_TERMS), **f32)
+            sc = N.MwFloatShapeConfig(
+                (ctypes.c_float * N.FLOAT_SHAPE_TERMS)(*weights.tolist()),
+                float(self.home_base[2]) if base_height_target is None else base_height_target, soft_limit,
+                collision_force_min, stumble_ratio, max_contact_force, termination_force, len(pen), len(term),
+                ip(pen), ip(term))
+            ptr = lambda t: ctypes.c_void_p(t.data_ptr())
+            N.check(N.lib().mw_floatenv_shaping(
+                h, ctypes.byref(sc), ptr(self.reward_terms), ptr(self.torques), ptr(self.episode_return),
+                ptr(self.episode_length), ptr(self.episode_terms)), "mw_floatenv_shaping")
+            self._info.update(reward_terms=self.reward_terms, torques=self.torques,
+                              episode_return=self.episode_return, episode_length=self.episode_length,
+                              episode_terms=self.episode_terms)
+
     def _noise_vector(self, obs_noise) -> np.ndarray:
         """obs_noise (group name -> amplitude, or obs_dim values) as the float32 vector the library takes."""
         if isinstance(obs_noise, Mapping):
@@ -397,6 +479,8 @@ class FloatVecEnv:
                     contact_links=("l_foot", "r_foot"), z_min=0.3, max_tilt=1.0, pgs_iters=50)
         if kw.get("task") == "locomotion":
             args.update(cls.LOCOMOTION_DEFAULTS)
+        # no shaping default here: the shipped model has collision shapes on the
+        # soles alone, so no other link (root link, chest) can report a contact
         args.update(kw)
         return cls("icub", n_worlds, **args)
 
@@ -408,16 +492,20 @@ class FloatVecEnv:
                     contact_links=("shank_fl", "shank_fr", "shank_hl", "shank_hr"), z_min=0.15, max_tilt=1.0)
         if kw.get("task") == "locomotion":
             args.update(cls.LOCOMOTION_DEFAULTS)
+        if kw.get("reward_terms") and "termination_links" not in kw:
+            # shaping in use: a quadruped on its trunk has fallen (the thighs of
+            # the shipped model carry no collision shape, so none is penalised)
+            args.update(termination_links=("trunk",))
         args.update(kw)
         return cls("quadruped", n_worlds, **args)
 
     # ------------------------------------------------------------------
-    def _resolve_links(self, model_file: str, links: Sequence):
+    def _resolve_links(self, model_file: str, links: Sequence, limit: Optional[int] = MAX_CONTACT_LINKS):
         """Link names / dof indices -> the dof index of the link's body (-1 =
         the base); a link welded to its parent by fixed joints counts as the
         body it is lumped into (the iCub's soles sit on the ankles' bodies)."""
-        if len(links) > MAX_CONTACT_LINKS:
-            raise ValueError(f"at most {MAX_CONTACT_LINKS} contact links")
+        if limit is not None and len(links) > limit:
+            raise ValueError(f"at most {limit} contact links")
         known = {self.sim.base_frame: -1}
         known.update({name: i for i, name in enumerate(self.sim.link_names)})
         fixed = None

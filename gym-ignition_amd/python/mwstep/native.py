@@ -162,6 +162,26 @@ class MwFloatNoiseConfig(ctypes.Structure):
 FLOAT_MAX_ACTION_DELAY = 8
 
 
+FLOAT_SHAPE_TERMS = 10
+
+
+class MwFloatShapeConfig(ctypes.Structure):
+    """mw_float_shape_config (include/mwstep.h)."""
+    _fields_ = [
+        ("weights", ctypes.c_float * FLOAT_SHAPE_TERMS),
+        ("base_height_target", ctypes.c_float),
+        ("soft_limit", ctypes.c_float),
+        ("collision_force_min", ctypes.c_float),
+        ("stumble_ratio", ctypes.c_float),
+        ("max_contact_force", ctypes.c_float),
+        ("termination_force", ctypes.c_float),
+        ("n_penalised_links", ctypes.c_int32),
+        ("n_termination_links", ctypes.c_int32),
+        ("penalised_links", ctypes.POINTER(ctypes.c_int32)),
+        ("termination_links", ctypes.POINTER(ctypes.c_int32)),
+    ]
+
+
 # (name, restype, argtypes) of every symbol in include/mwstep.h
 _P = ctypes.c_void_p
 _I = ctypes.c_int32
@@ -263,6 +283,7 @@ SIGNATURES = [
     ("mw_floatenv_joints", ctypes.c_int, [_P, ctypes.POINTER(MwFloatJointConfig), _P, _P]),
     ("mw_floatenv_noise", ctypes.c_int, [_P, ctypes.POINTER(MwFloatNoiseConfig), ctypes.POINTER(ctypes.c_float),
                                          _P, _P, _P]),
+    ("mw_floatenv_shaping", ctypes.c_int, [_P, ctypes.POINTER(MwFloatShapeConfig), _P, _P, _P, _P, _P]),
 ]
 
 # include/mwscene.h

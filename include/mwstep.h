@@ -743,6 +743,93 @@ typedef struct {
 int mw_floatenv_noise(mw_vecenv* env, const mw_float_noise_config* cfg, const float* amplitude /* host, obs_dim words or NULL */,
                       float* clean_obs_dev, float* clean_terminal_obs_dev, int32_t* delay_dev);
 
+/* Shaping rewards, contact termination and per-episode statistics of a
+ * floating-base env, computed inside the step's three launches (no host copy,
+ * capturable); off unless configured, and with it off every output is what it
+ * was.  Call it after mw_floatenv_create and before the first mw_vecenv_reset
+ * (MW_ESTATE after it, or on another kind of env), and after
+ * mw_floatenv_locomotion where weights[9] (stand_still) is set (MW_ESTATE
+ * without the locomotion task).  A refused call leaves the env as it was; a
+ * config of all zeros without links returns it as made.
+ *   terms    ten columns in fixed order; column k of a world's row is the signed
+ *            contribution -weights[k] x_k of the step, 0 where weights[k] is 0:
+ *              0 torque         sum_d tau_d^2
+ *              1 power          sum_d |tau_d qd_d|
+ *              2 joint_acc      sum_d ((qd_d - qd_d of the last step) / env_dt)^2,
+ *                               env_dt = steps_per_run step_size; from rest on
+ *                               an episode's first step
+ *              3 orientation    g_x^2 + g_y^2 of the projected gravity (world -z
+ *                               in the body frame)
+ *              4 base_height    (z - base_height_target)^2
+ *              5 joint_limits   sum_d max(0, lo_d - q_d) + max(0, q_d - hi_d), lo
+ *                               / hi = centre -/+ soft_limit half-range of the
+ *                               position limits; a joint without finite limits
+ *                               contributes nothing
+ *              6 collision      number of penalised_links whose contact force
+ *                               norm exceeds collision_force_min
+ *              7 stumble        number of contact links (mw_float_task_config)
+ *                               with hypot(f_x, f_y) > stumble_ratio |f_z| and
+ *                               |f_z| > 0
+ *              8 contact_force  sum over the contact links of max(0, |f| -
+ *                               max_contact_force)
+ *              9 stand_still    sum_d |q_d - home_q_d| where the command the step
+ *                               ran under has v_x^2 + v_y^2 <= cmd_min^2, else 0
+ *            A link's f is the sum of the force vectors of its active contact
+ *            points, in world axes.  tau_d is the torque the run applied:
+ *            clamp(u_d, +-effort_d) with u_d the JointController's last output
+ *            (position mode) or the command the run received, after scaling
+ *            and latency (torque mode, where it acts on the first physics step
+ *            of the run); effort_d is the limit the run clamped with, the
+ *            world's own under mw_set_joint_dynamics / mw_floatenv_joints.
+ *            Every product and sum has a defined float32 rounding
+ *            (csrc/float_task.hpp); sums over dofs or links are taken as four
+ *            partial sums, item i in partial i % 4, added in order.
+ *   reward   the reward of the env as configured so far, then + term 0 ... +
+ *            term 9 in that order.
+ *   done     additionally terminated -- not truncated: the alive bonus is lost,
+ *            as for z_min -- when a contact point of a termination link is
+ *            active with a force norm above termination_force.  Contacts here
+ *            and in the terms are those of the LAST physics step of the run
+ *            (what mw_get_contacts shows), not of every step of it: with
+ *            steps_per_run > 1 a touch that ends before the run's last physics
+ *            step is not seen.
+ *   diverged a world flagged diverged reports ten zeros and adds nothing to its
+ *            running sums: its state is not finite, and the episode ends.
+ *   stats    per world the running return (the sum of reward as written), the
+ *            length and the ten term sums of the current episode; where done is
+ *            set they are copied to ep_return_dev / ep_length_dev / ep_terms_dev
+ *            and zeroed.  mw_vecenv_reset zeroes the running sums and leaves the
+ *            finished-episode buffers alone; a world's entries are valid once it
+ *            has been done.
+ * penalised_links (at most 8) and termination_links (any number) are dof
+ * indices of links, -1 = the base, as contact_links.  A link of either list
+ * that owns none of the 32 contact slots of the wave kernel's mask -- no
+ * collision shape, or only slots >= 32 -- is refused with MW_EINVAL, since it
+ * could never fire; so are weights[6] without penalised links and weights[7] /
+ * weights[8] without contact links, a negative weight or threshold, a
+ * non-finite field and soft_limit outside (0, 1].
+ * terms_dev float32 [n_worlds, 10], torque_dev float32 [n_worlds, n_dofs] (the
+ * tau the terms used, written every step whatever the weights),
+ * ep_return_dev float32 [n_worlds], ep_length_dev int32 [n_worlds] and
+ * ep_terms_dev float32 [n_worlds, 10] are caller-owned device buffers (each may
+ * be NULL) that must outlive the env. */
+#define MW_FLOAT_SHAPE_TERMS 10
+typedef struct {
+    float weights[MW_FLOAT_SHAPE_TERMS]; /* >= 0, in the order above             */
+    float base_height_target;            /* m                                   */
+    float soft_limit;                    /* in (0, 1]                           */
+    float collision_force_min;           /* N, >= 0                             */
+    float stumble_ratio;                 /* >= 0                                */
+    float max_contact_force;             /* N, >= 0                             */
+    float termination_force;             /* N, >= 0                             */
+    int32_t n_penalised_links;           /* <= 8                                */
+    int32_t n_termination_links;
+    const int32_t* penalised_links;      /* [n_penalised_links] dof index, -1 = base */
+    const int32_t* termination_links;    /* [n_termination_links] likewise      */
+} mw_float_shape_config;
+int mw_floatenv_shaping(mw_vecenv* env, const mw_float_shape_config* cfg, float* terms_dev, float* torque_dev,
+                        float* ep_return_dev, int32_t* ep_length_dev, float* ep_terms_dev);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,18 @@ kernel with its ring), fed the same home-posture targets -- the delayed and
 the neutral command are both the home posture, so the run does the same work
 -- and reports env_noise - env.
 
+--shaping adds two envs to the alternation: env_sbase, the velocity-command
+task as --task locomotion times it, and env_shape, the same with all ten
+shaping terms weighted, a termination and a penalised link list and every
+output buffer attached (mw_floatenv_shaping: the shaping branch of the post
+kernel), both fed zero actions -- the same physics -- and reports env_shape -
+env_sbase beside the bytes the branch moves per world and step, counted from
+the kernel: per dof q, qd, the kept qd, the controller output and the effort
+word read and the kept qd and the torque written (28 n), the contact mask
+again (4), three force words per active contact slot and list that names its
+link (12 S), the twelve running sums read and written (96) and the row of
+terms (40).
+
 Not a bench.py leg.  Prints one JSON line per model."""
 
 import argparse
@@ -81,6 +93,14 @@ JOINT_DOFS = {"quadruped": None,
 NOISE = dict(obs_noise=dict(base_position=0.01, base_orientation=0.01, base_linear_velocity=0.1,
                             base_angular_velocity=0.05, joint_positions=0.01, joint_velocities=0.5, contacts=2.0),
              action_delay_range=(0, 3))
+# --shaping: all ten terms; links that carry a collision shape (the iCub's soles are its only ones: their
+# termination force is out of reach, so that no episode ends inside the timed windows)
+SHAPING = dict(reward_terms=dict(torque=2e-5, power=1e-4, joint_acc=2.5e-7, orientation=1.0, base_height=10.0,
+                                 joint_limits=5.0, collision=1.0, stumble=0.5, contact_force=0.01, stand_still=0.2),
+               collision_force_min=0.1, stumble_ratio=5.0, max_contact_force=50.0)
+SHAPING_LINKS = {"quadruped": dict(termination_links=("trunk",), penalised_links=("trunk",), termination_force=1.0),
+                 "icub": dict(termination_links=("l_foot", "r_foot"), penalised_links=("l_foot", "r_foot"),
+                              termination_force=1e6)}
 sys.path.insert(0, os.path.join(ROOT, "gym-ignition_amd", "python"))
 
 
@@ -189,6 +209,17 @@ def measure(torch, args, model, W):
             noisy = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0, **NOISE)
             noisy.reset()
         graphs["env_noise"] = capture(torch, stream, lambda: noisy.step_raw(actions.data_ptr()), args.warmup)
+    sbase = shaped = None
+    if args.shaping:
+        with torch.cuda.stream(stream):
+            sbase = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0, **LOCOMOTION)
+            sbase.reset()
+            shaped = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0, **LOCOMOTION, **SHAPING,
+                                                 **SHAPING_LINKS[model])
+            shaped.reset()
+            szeros = torch.zeros((W, shaped.action_dim), dtype=torch.float32, device=shaped.device)
+        graphs["env_sbase"] = capture(torch, stream, lambda: sbase.step_raw(szeros.data_ptr()), args.warmup)
+        graphs["env_shape"] = capture(torch, stream, lambda: shaped.step_raw(szeros.data_ptr()), args.warmup)
     times = {k: [] for k in graphs}
     for _ in range(args.rounds):
         for k, g in graphs.items():
@@ -270,6 +301,23 @@ def measure(torch, args, model, W):
                     "clean_row_bytes_per_step": W * env.obs_dim * 4, "ring_bytes": ring,
                     "noise_base_z_range_after": [round(float(zn.min()), 4), round(float(zn.max()), 4)]})
         noisy.close()
+    if shaped is not None:
+        n = env.action_dim
+        lists = [shaped.contact_links, shaped.penalised_links, shaped.termination_links]
+        slots = sum(int((shaped.sim.contact_bodies(w)[:, None] == np.asarray(links)[None, :]).sum())
+                    for w in range(min(W, 64)) for links in lists) / min(W, 64)
+        terms = shaped.reward_terms.cpu().numpy()
+        out.update({"env_sbase_step_us": round(med["env_sbase"], 3), "env_shape_step_us": round(med["env_shape"], 3),
+                    "shape_minus_sbase_us": round(med["env_shape"] - med["env_sbase"], 3),
+                    "shape_share_of_step": round((med["env_shape"] - med["env_sbase"]) / med["env_shape"], 4),
+                    "shaping": {**SHAPING, **SHAPING_LINKS[model]},
+                    "shape_state_equals_sbase_state": bool((shaped.sim.get_state() == sbase.sim.get_state()).all()),
+                    "shape_active_slot_reads_per_world": round(slots, 2),
+                    "shape_bytes_per_world_step": round(28 * n + 4 + 12 * slots + 96 + 40, 1),
+                    "shape_terms_nonzero_columns": [int(k) for k in np.flatnonzero((terms != 0).any(axis=0))],
+                    "shape_episodes_finished": int(shaped.counters()[0].sum().item())})
+        sbase.close()
+        shaped.close()
     env.close()
     sim.close()
     return out
@@ -292,6 +340,9 @@ def main():
                         "(env_joints)")
     p.add_argument("--noise", action="store_true",
                    help="also time an env with observation noise and action latency on (env_noise)")
+    p.add_argument("--shaping", action="store_true",
+                   help="also time the locomotion env without (env_sbase) and with (env_shape) the shaping terms, "
+                        "contact termination and episode statistics")
     p.add_argument("--task", choices=("forward", "locomotion"), default="forward",
                    help="locomotion: also time an env with the velocity-command task on (env_loco)")
     args = p.parse_args()
