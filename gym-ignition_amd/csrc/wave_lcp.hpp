@@ -203,9 +203,18 @@ __device__ __forceinline__ float lcp_row_residual(bool live, float b, float xl, 
     float e;
     if (xl < L - tolx || xl > U + tolx)
         e = ((xl < L) ? (L - xl) : (xl - U)) * arr;
-    else if (U - L <= tolx)
-        e = 0.f;
-    else if (xl <= L + tolx)
+    else if (U - L <= tolx) {
+        // a box narrower than the impulse tolerance: any point of it will do,
+        // as long as crossing it moves the row's own velocity by no more than
+        // the velocity tolerance.  On a light link it can move it by more (A_rr
+        // ~ 300 rad/s per N m s on a 0.2 kg leaf: a joint friction of 1e-3 N m,
+        // a box of 2e-6 N m s, is worth 6e-4 rad/s): then the nearer bound is
+        // the row's, with the sign condition of that bound
+        if ((U - L) * arr <= kLcpRelTol * (fabsf(b) + mag) + kLcpAbsTol)
+            e = 0.f;
+        else
+            e = (xl - L <= U - xl) ? fmaxf(s, 0.f) : fmaxf(-s, 0.f);
+    } else if (xl <= L + tolx)
         e = fmaxf(s, 0.f);
     else if (xl >= U - tolx)
         e = fmaxf(-s, 0.f);
@@ -213,6 +222,33 @@ __device__ __forceinline__ float lcp_row_residual(bool live, float b, float xl, 
         e = fabsf(s);
     e_abs = e;
     return e * rcp(kLcpRelTol * (fabsf(b) + mag) + kLcpAbsTol);
+}
+
+// A pivot of the elimination of a symmetric positive definite system in lane
+// order.  In exact arithmetic it is positive; where fp32 cannot resolve it (a
+// joint beyond its limit that also has Coulomb friction: its two rows are one
+// Jacobian row twice, their Schur pivot is DART's joint CFM, 1e-9, below the
+// rounding of A_rr) the computed value is rounding noise of either sign.  Its
+// magnitude stands in: the degenerate row's unknown then grows large in the
+// direction exact arithmetic gives it, and the active-set step's blocking
+// bound resolves the pair.  With the noise's own sign the row moved the other
+// way half the time, was blocked at zero length at the bound it had just been
+// released from and frozen there, and the world-step ended unconverged (same
+// velocities -- the pair's impulses only swap -- but a wrongly signed
+// multiplier).  A positive pivot is returned bit for bit.
+// Every elimination of this file goes through it -- lcp_ge_solve in lane order
+// (the paired LongRows steps of the scene kernel's long rows included) and the
+// matrix-core LDL^T -- so the scene kernel's LCPs (scene_kernel.hip) take the
+// same guard as the wave kernel's.
+__device__ __forceinline__ float spd_pivot(float p) {
+    const float m = fabsf(p);
+    return (m < 1e-30f) ? 1e-30f : m;
+}
+// lcp_ge_solve's pivot: with the pivot search the rows are permuted and the
+// pivot keeps its sign (only an exact zero is guarded); in lane order the
+// system is symmetric positive definite
+__device__ __forceinline__ float ge_pivot(float p, bool searched) {
+    return searched ? ((fabsf(p) < 1e-30f) ? 1e-30f : p) : spd_pivot(p);
 }
 
 // Gaussian elimination with partial pivoting, lane = row: k[c] = K[lane][c],
@@ -308,10 +344,10 @@ __device__ __forceinline__ float lcp_ge_solve(float (&k)[RC], float rhs, int n, 
             const float4* us = reinterpret_cast<const float4*>(rowS);
             float4 a = ua[0], sv = us[0];
             const float arhs = rowA[kLcpRhs], srhs = rowS[kLcpRhs];
-            const float pa = (fabsf(a.x) < 1e-30f) ? 1e-30f : a.x;
+            const float pa = spd_pivot(a.x);
             const float g = sv.x * rcp(pa);
             const float b1 = fmaf(-g, a.y, sv.y);
-            const float pb = (fabsf(b1) < 1e-30f) ? 1e-30f : b1;
+            const float pb = spd_pivot(b1);
             const float brhs = fmaf(-g, arhs, srhs);
             const bool wb = lane == j + 1;
             const bool act = !(used || lane == j || wb);
@@ -374,7 +410,7 @@ __device__ __forceinline__ float lcp_ge_solve(float (&k)[RC], float rhs, int n, 
         const float4* ur = reinterpret_cast<const float4*>(row);
         float4 cur = ur[0];
         const float prhs = row[kLcpRhs];
-        const float piv = (fabsf(cur.x) < 1e-30f) ? 1e-30f : cur.x;
+        const float piv = ge_pivot(cur.x, pivot);
         const float f = (used || lane == p) ? 0.f : k[0] * rcp(piv);
 #pragma unroll
         for (int c = 0; c < RC; c += 4) {
@@ -395,7 +431,7 @@ __device__ __forceinline__ float lcp_ge_solve(float (&k)[RC], float rhs, int n, 
     if (lane < n && mask_bit(cols, lane)) {
         acc = U[lane * kLcpUStride + (boff ? 0 : kLcpRhs)];
         float dg = U[lane * kLcpUStride + boff];
-        dg = (fabsf(dg) < 1e-30f) ? 1e-30f : dg;
+        dg = ge_pivot(dg, pivot);
         rdiag = rcp(dg);
     }
     float dl = 0.f;
@@ -453,14 +489,15 @@ __device__ __forceinline__ void mfma_pivot(const v16f& T, float& i0, float& l, f
     constexpr int i = 4 * (J / 8) + (J % 4), hl = 32 * ((J / 4) % 2);
     const float s00 = read_lane(T[i], J + hl), s01 = read_lane(T[i], J + 1 + hl);
     const float s11 = read_lane(T[i + 1], J + 1 + hl);
-    // a zero pivot (two identical joint rows: DART's joint CFM, 1e-9, is below
-    // fp32's resolution) takes the elimination's guard (lcp_ge_solve): its
-    // column is exactly zero, the row's unknown grows large and the active-set
-    // step's blocking bound resolves the degenerate pair
-    i0 = rcp((fabsf(s00) < 1e-30f) ? 1e-30f : s00);
+    // a zero or negative pivot (two identical joint rows: DART's joint CFM,
+    // 1e-9, is below fp32's resolution) takes the elimination's guard
+    // (spd_pivot, as lcp_ge_solve and with it the scene kernel's solves do):
+    // the row's unknown grows large in the direction exact arithmetic gives it
+    // and the active-set step's blocking bound resolves the degenerate pair
+    i0 = rcp(spd_pivot(s00));
     l = s01 * i0;
     const float d1 = fmaf(-l, s01, s11);
-    i1 = rcp((fabsf(d1) < 1e-30f) ? 1e-30f : d1);
+    i1 = rcp(spd_pivot(d1));
 }
 // this lane's panel entry P[lane % 32][J + lane / 32] of tile T
 template <int J>

@@ -15,6 +15,7 @@ the per-link contact force sums (another summation order) within
 
 import ctypes
 import math
+import os
 
 import numpy as np
 import pytest
@@ -31,7 +32,9 @@ def _twin(env, model, gains=None):
     from mwstep import native as N
     from mwstep.sim import Simulator
     s = env.sim
-    twin = Simulator(get_model_file(model), n_worlds=env.n_worlds, step_size=s.step_size,
+    if not (model.lstrip().startswith("<") or os.path.exists(model)):      # else: a URDF text or file
+        model = get_model_file(model)
+    twin = Simulator(model, n_worlds=env.n_worlds, step_size=s.step_size,
                      steps_per_run=s.steps_per_run, pgs_iters=env._pgs_iters, pose=tuple(env.home_base.tolist()))
     twin.set_ground_plane(True, 1.0)
     twin.enable_contacts(True)

@@ -42,27 +42,37 @@ TOL = dict(pose=1e-5, q=1e-5, point=1e-5, vel=2e-3, qd=2e-3, force=5e-3)
 TREE_PARENTS = [-1, 0, 1, 1, 3, 3, 0, 6, -1, 8, 8, 8, 11, 2, -1, 14]
 
 
-def tree_urdf(parents=TREE_PARENTS, seed=5, damping=0.0, cylinders=False):
+def tree_urdf(parents=TREE_PARENTS, seed=5, damping=0.0, cylinders=False, friction=0.0, friction_every=2,
+              unlimited=False, welded=False):
     """A floating box base with a random branched tree: revolute / prismatic
     joints about random unit axes, random origins and masses, a sphere on
     every leaf; `damping` > 0 adds viscous joint damping of that size times a
     random factor in [0.5, 1.5] to every joint; `cylinders`: a cylinder base
     and cylinders on the first two leaves (Physics.cpp builds cylinder
-    collisions; 8 rim slots each)."""
+    collisions; 8 rim slots each); `friction` > 0: Coulomb friction of that
+    size on every `friction_every`-th joint; `unlimited`: every joint is a
+    `continuous` one (no limit anywhere); `welded`: the base is welded to the
+    world at 1.5 m.  The options draw nothing: a tree keeps its frames, axes
+    and masses under every one of them."""
     rng = np.random.default_rng(seed)
     base_geo = ('<origin rpy="0 1.5708 0"/><geometry><cylinder radius="0.12" length="0.4"/></geometry>'
                 if cylinders else '<geometry><box size="0.4 0.3 0.12"/></geometry>')
     parts = ['<link name="base"><inertial><mass value="4.0"/>'
              '<inertia ixx="0.05" iyy="0.06" izz="0.07" ixy="0.002" ixz="0" iyz="0"/></inertial>'
              f'<collision>{base_geo}</collision></link>']
+    if welded:
+        parts.insert(0, '<link name="world"/><joint name="weld" type="fixed"><parent link="world"/>'
+                        '<child link="base"/><origin xyz="0 0 1.5"/></joint>')
     leaves = set(range(len(parents))) - {p for p in parents if p >= 0}
     cyl_leaves = set(sorted(leaves)[:2]) if cylinders else set()
     for i, pa in enumerate(parents):
         axis = rng.normal(size=3)
         axis /= np.linalg.norm(axis)
-        prismatic = i % 5 == 4
+        prismatic = i % 5 == 4 and not unlimited
         lim = ('<limit lower="-0.2" upper="0.2" effort="80" velocity="10"/>' if prismatic else
                '<limit lower="-1.5" upper="1.5" effort="50" velocity="30"/>')
+        if unlimited:
+            lim = '<limit effort="50" velocity="30"/>'
         xyz = " ".join(f"{v:.3f}" for v in rng.uniform(-0.15, 0.15, 3))
         rpy = " ".join(f"{v:.3f}" for v in rng.uniform(-0.5, 0.5, 3))
         tip = ('<collision><origin xyz="0 0 -0.1" rpy="0.3 0 0.2"/><geometry><cylinder radius="0.03" '
@@ -71,8 +81,11 @@ def tree_urdf(parents=TREE_PARENTS, seed=5, damping=0.0, cylinders=False):
                if i in leaves else "")
         m = rng.uniform(0.2, 1.0)
         dyn = f'<dynamics damping="{damping * rng.uniform(0.5, 1.5):.4f}"/>' if damping > 0 else ""
+        if friction > 0 and i % friction_every == 0:
+            dyn = dyn[:-2] + f' friction="{friction}"/>' if dyn else f'<dynamics friction="{friction}"/>'
         parent = "base" if pa < 0 else f"l{pa}"
-        parts.append(f'<joint name="j{i}" type="{"prismatic" if prismatic else "revolute"}">'
+        jtype = "prismatic" if prismatic else "continuous" if unlimited else "revolute"
+        parts.append(f'<joint name="j{i}" type="{jtype}">'
                      f'<parent link="{parent}"/><child link="l{i}"/><origin xyz="{xyz}" rpy="{rpy}"/>'
                      f'<axis xyz="{axis[0]:.4f} {axis[1]:.4f} {axis[2]:.4f}"/>{lim}{dyn}</joint>'
                      f'<link name="l{i}"><inertial><origin xyz="0 0.01 -0.05"/><mass value="{m:.3f}"/>'
@@ -89,6 +102,8 @@ def _model(name):
         return tree_urdf()
     if name == "tree16d":  # joint damping: DART's implicit damping + the dual (impulse) recursion
         return tree_urdf(damping=2.0)
+    if name == "tree16f":  # Coulomb friction on every second joint: beyond its limit such a joint has one row twice
+        return tree_urdf(friction=0.3)
     if name == "tree16c":  # cylinder collisions on the base and two leaves
         return tree_urdf(cylinders=True)
     if name.endswith("c"):
@@ -108,16 +123,23 @@ def _model(name):
                                           ("chain2c", "lane"), ("chain2c", "wave"), ("tree16c", "wave"),
                                           ("chain2m", "lane"), ("chain2m", "wave")])
 def test_one_step_parity_with_contacts(require_gpu, oracle, monkeypatch, name, kernel):
+    one_step_parity(oracle, monkeypatch, _model(name), name, kernel)
+
+
+def one_step_parity(oracle, monkeypatch, text, name, kernel, states=None):
+    """The body of test_one_step_parity_with_contacts (shared with
+    test_gpu_big_tree.py); states: (q, qd, pose, vel, tau) of 256 worlds,
+    default the random states of seed 11.  Returns the worst errors."""
     from mwstep import native as N
     from mwstep.sim import Simulator
-    text = _model(name)
     monkeypatch.setenv("MWSTEP_WAVE_TREE", "1" if kernel == "wave" else "0")
     W, pgs, mu = 256, 50, 0.8
     rng = np.random.default_rng(11)
     cm = oracle.load_urdf(text)
-    q, qd, pose, vel, tau = _random_states(cm, W, rng)
+    q, qd, pose, vel, tau = states if states is not None else _random_states(cm, W, rng)
     sim = Simulator(text, n_worlds=W, pgs_iters=pgs)
     assert sim.float_kernel() == (2 if kernel == "wave" else 1)
+    assert sim.dofs == cm.n
     if kernel == "wave":
         # kernel arithmetic against the same algorithm (PGS-50); the exact
         # solve on these adversarial states: test_one_step_exact_lcp_random_states
@@ -192,10 +214,11 @@ def test_one_step_parity_with_contacts(require_gpu, oracle, monkeypatch, name, k
     assert worst["pose"] <= TOL["pose"] and worst["q"] <= TOL["q"] and worst["point"] <= TOL["point"]
     assert worst["vel"] <= TOL["vel"] and worst["qd"] <= TOL["qd"] and worst["force"] <= TOL["force"]
     sim.close()
+    return worst
 
 
 @pytest.mark.parametrize("name", ["icub", "quadruped", "tree16", "chain2c", "chain2", "tree16d", "tree16c",
-                                  "chain2m"])
+                                  "chain2m", "tree16f"])
 def test_one_step_exact_lcp_random_states(require_gpu, oracle, monkeypatch, name):
     """The exact LCP solve (wave_lcp.hpp, the wave kernel's default) on the
     adversarial random states of test_one_step_parity_with_contacts (bodies
@@ -224,16 +247,23 @@ def test_one_step_exact_lcp_random_states(require_gpu, oracle, monkeypatch, name
     had run out of its 24-solve budget at a complementarity error 3,600x
     the tolerance -- the default budget is 48 since, and it converges in
     32).  The agreeing worlds' own backward errors are printed too."""
+    one_step_exact_lcp(oracle, monkeypatch, _model(name), name)
+
+
+def one_step_exact_lcp(oracle, monkeypatch, text, name, states=None):
+    """The body of test_one_step_exact_lcp_random_states (shared with
+    test_gpu_big_tree.py); states as in one_step_parity.  Returns
+    exact_lcp_acceptance's record."""
     from mwstep import native as N
     from mwstep.sim import Simulator
-    text = _model(name)
     monkeypatch.setenv("MWSTEP_WAVE_TREE", "1")
     W, mu = 256, 0.8
     rng = np.random.default_rng(11)
     cm = oracle.load_urdf(text)
-    q, qd, pose, vel, tau = _random_states(cm, W, rng)
+    q, qd, pose, vel, tau = states if states is not None else _random_states(cm, W, rng)
     sim = Simulator(text, n_worlds=W, pgs_iters=50)
     assert sim.float_kernel() == 2 and sim.lcp_solver() == (True, 48)
+    assert sim.dofs == cm.n
     sim.set_ground_plane(True, mu)
     sim.enable_contacts(True)
     sim.set("reset_q", q)
@@ -249,9 +279,10 @@ def test_one_step_exact_lcp_random_states(require_gpu, oracle, monkeypatch, name
     p1, gq1, gqd1 = sim.base_pose(), sim.get("q"), sim.get("qd")
     state = sim.get_state()
     dump = (lambda prob, w: _dump_lcp(prob, f"random_{name}_{w}")) if os.environ.get("MW_TEST_DUMP_LCP") else None
-    exact_lcp_acceptance(sim, oracle, cm, mu, tau, (p0, v0, gq0, gqd0), (p1, gq1, gqd1, state), label=name,
-                         dump=dump)
+    out = exact_lcp_acceptance(sim, oracle, cm, mu, tau, (p0, v0, gq0, gqd0), (p1, gq1, gqd1, state), label=name,
+                               dump=dump)
     sim.close()
+    return out
 
 
 def test_exact_lcp_out_of_budget_is_feasible(require_gpu, oracle, monkeypatch):
