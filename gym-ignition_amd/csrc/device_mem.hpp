@@ -7,6 +7,7 @@
 
 #include <memory>
 #include <type_traits>
+#include <utility>
 
 namespace mw {
 
@@ -29,6 +30,15 @@ hipError_t dev_alloc(dev_ptr<T>& out, size_t bytes) {
     void* p = nullptr;
     const hipError_t e = hipMalloc(&p, bytes);
     if (e == hipSuccess) out.reset(static_cast<typename dev_ptr<T>::pointer>(p));
+    return e;
+}
+// ... and the new buffer is zeroed on `stream` first
+template <typename T>
+hipError_t dev_alloc_zeroed(dev_ptr<T>& out, size_t bytes, hipStream_t stream) {
+    dev_ptr<T> p;
+    hipError_t e = dev_alloc(p, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(p.get(), 0, bytes, stream);
+    if (e == hipSuccess) out = std::move(p);
     return e;
 }
 template <typename T>

@@ -1,5 +1,6 @@
 // errors.hpp -- the thread-local last error behind mw_last_error() (sim.cpp)
-// and the result helpers of the host layer (sim.cpp, world_params.cpp, vecenv.cpp, scene.cpp).
+// and the result helpers of the host layer (sim.cpp, world_params.cpp, vecenv.cpp,
+// floatenv.cpp, scene.cpp).
 #pragma once
 
 #include <cstring>

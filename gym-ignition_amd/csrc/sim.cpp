@@ -31,7 +31,7 @@ using mw::to_f32;
 
 static thread_local std::string g_last_error;
 
-// the calling thread's last error (mw_last_error), shared with vecenv.cpp and scene.cpp
+// the calling thread's last error (mw_last_error), shared with vecenv.cpp, floatenv.cpp and scene.cpp
 void mw::set_last_error(const std::string& msg) { g_last_error = msg; }
 
 int check_sim(const mw_sim* s, bool need_init) {

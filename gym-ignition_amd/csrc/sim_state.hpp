@@ -1,5 +1,6 @@
 // sim_state.hpp -- the simulator behind an mw_sim handle and the helpers
-// sim.cpp, world_params.cpp and the batched envs (vecenv.cpp) share.  Internal, host only.
+// sim.cpp, world_params.cpp and the batched envs (vecenv.cpp, floatenv.cpp) share.
+// Internal, host only.
 #pragma once
 
 #include "mwstep.h"
@@ -191,7 +192,7 @@ struct mw_sim {
     }
 };
 
-// sim.cpp, shared with the batched envs (vecenv.cpp)
+// sim.cpp, shared with the batched envs (vecenv.cpp, floatenv.cpp)
 int check_sim(const mw_sim* s, bool need_init = true);
 int run_impl(mw_sim* s, int paused, bool readback);
 bool needs_cons(const mw_sim* s);

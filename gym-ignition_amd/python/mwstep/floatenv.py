@@ -80,6 +80,20 @@ def _torch():
     return torch
 
 
+def _ptr(t):
+    """The device pointer of a tensor for the C layer; None (a feature that is off) stays None."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _fptr(a: np.ndarray):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+
+
+def _iptr(a: np.ndarray):
+    """An int32 list of the C layer; an empty one is passed as NULL."""
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if len(a) else None
+
+
 def _fixed_parents(model: str) -> Dict[str, str]:
     """child link -> parent link of every fixed joint of a URDF (file or text):
     the model compiler lumps such a child into the body of its parent."""
@@ -296,23 +310,14 @@ class FloatVecEnv:
         cfg = N.MwFloatTaskConfig(
             ACTION_MODES[action_mode], max_episode_steps, world_offset, len(links), seed & 0xFFFFFFFFFFFFFFFF,
             z_min, math.cos(max_tilt), alive_bonus, w_forward, w_action, w_pose, joint_noise, 0.0,
-            (ctypes.c_float * 7)(*self.home_base.tolist()),
-            self.home_q.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-            links.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if len(links) else None)
+            (ctypes.c_float * 7)(*self.home_base.tolist()), _fptr(self.home_q), _iptr(links))
         h = ctypes.c_void_p()
         N.check(N.lib().mw_floatenv_create(sim.handle, ctypes.byref(cfg), ctypes.byref(h)), "mw_floatenv_create")
         self._h = h
-        f32 = dict(dtype=torch.float32, device=self.device)
-        self.command = None
-        if task == "locomotion":
-            self.command = torch.zeros((n_worlds, 3), **f32)
-            lc = N.MwFloatLocoConfig(
-                (ctypes.c_float * 3)(*[float(r[0]) for r in command_ranges]),
-                (ctypes.c_float * 3)(*[float(r[1]) for r in command_ranges]),
-                cmd_interval, cmd_zero_prob, cmd_min, action_scale, w_track_lin, w_track_yaw, track_sigma,
-                w_lin_z, w_ang_xy, w_action_rate, w_air_time, air_time_target, contact_force_min)
-            N.check(N.lib().mw_floatenv_locomotion(h, ctypes.byref(lc), ctypes.c_void_p(self.command.data_ptr())),
-                    "mw_floatenv_locomotion")
+        # the C layer takes the locomotion task first: it sets the width of the rows
+        self._setup_locomotion(command_ranges, cmd_interval, cmd_zero_prob, cmd_min, action_scale, w_track_lin,
+                               w_track_yaw, track_sigma, w_lin_z, w_ang_xy, w_action_rate, w_air_time,
+                               air_time_target, contact_force_min)
         no = ctypes.c_int32()
         N.check(N.lib().mw_vecenv_obs_dim(h, ctypes.byref(no)))
         self.obs_dim = no.value
@@ -332,118 +337,157 @@ class FloatVecEnv:
         if task == "locomotion":
             self.noise_slices.update(gravity=slice(nb, nb + 3), body_linear_velocity=slice(nb + 3, nb + 6),
                                      body_angular_velocity=slice(nb + 6, nb + 9))
-        self.obs = torch.zeros((n_worlds, self.obs_dim), **f32)
-        self.reward = torch.zeros((n_worlds,), **f32)
-        self.done = torch.zeros((n_worlds,), dtype=torch.uint8, device=self.device)
-        self.terminal_obs = torch.zeros((n_worlds, self.obs_dim), **f32)
-        self.push = self.friction = None
+        self.obs = self._zeros(n_worlds, self.obs_dim)
+        self.reward = self._zeros(n_worlds)
+        self.done = self._zeros(n_worlds, dtype=torch.uint8)
+        self.terminal_obs = self._zeros(n_worlds, self.obs_dim)
+        # what step(), step_raw() and rollout() pass after the actions
+        self._out = tuple(_ptr(t) for t in (self.obs, self.reward, self.done, self.terminal_obs))
         self._info = {"terminal_obs": self.terminal_obs}
         if self.command is not None:
             self._info["command"] = self.command
-        if push_interval or friction_range is not None:
-            lo, hi = (0.0, 0.0) if friction_range is None else friction_range
-            if push_interval:
-                self.push = self._info["push"] = torch.zeros((n_worlds, 6), **f32)
-            if hi > 0:
-                self.friction = self._info["friction"] = torch.full((n_worlds,), float(ground_mu), **f32)
-            rc = N.MwFloatRandConfig(push_interval, push_steps, push_force, push_torque, lo, hi)
-            N.check(N.lib().mw_floatenv_randomize(
-                h, ctypes.byref(rc), None if self.push is None else ctypes.c_void_p(self.push.data_ptr()),
-                None if self.friction is None else ctypes.c_void_p(self.friction.data_ptr())), "mw_floatenv_randomize")
+        self._setup_randomize(push_interval, push_steps, push_force, push_torque, friction_range, ground_mu)
+        self._setup_inertia(mass_scale_range, payload_range, payload_box)
+        self._setup_joints(joint_damping_range, joint_friction_range, effort_scale_range, joint_rand_dofs)
+        self._setup_noise(obs_noise, action_delay_range)
+        self._setup_shaping(model_file, reward_terms, termination_links, termination_force, penalised_links,
+                            collision_force_min, base_height_target, soft_limit, stumble_ratio, max_contact_force)
 
+    def _zeros(self, *shape, dtype=None):
+        torch = _torch()
+        return torch.zeros(shape, dtype=dtype or torch.float32, device=self.device)
+
+    # One method per feature: its argument checks, its tensors, its config
+    # struct and its one C call.  A feature that is off leaves its attributes None.
+
+    def _setup_locomotion(self, command_ranges, cmd_interval, cmd_zero_prob, cmd_min, action_scale, w_track_lin,
+                          w_track_yaw, track_sigma, w_lin_z, w_ang_xy, w_action_rate, w_air_time, air_time_target,
+                          contact_force_min):
+        self.command = None
+        if self.task != "locomotion":
+            return
+        self.command = self._zeros(self.n_worlds, 3)
+        lc = N.MwFloatLocoConfig(
+            (ctypes.c_float * 3)(*[float(r[0]) for r in command_ranges]),
+            (ctypes.c_float * 3)(*[float(r[1]) for r in command_ranges]),
+            cmd_interval, cmd_zero_prob, cmd_min, action_scale, w_track_lin, w_track_yaw, track_sigma,
+            w_lin_z, w_ang_xy, w_action_rate, w_air_time, air_time_target, contact_force_min)
+        N.check(N.lib().mw_floatenv_locomotion(self._h, ctypes.byref(lc), _ptr(self.command)),
+                "mw_floatenv_locomotion")
+
+    def _setup_randomize(self, push_interval, push_steps, push_force, push_torque, friction_range, ground_mu):
+        self.push = self.friction = None
+        if not push_interval and friction_range is None:
+            return
+        lo, hi = (0.0, 0.0) if friction_range is None else friction_range
+        if push_interval:
+            self.push = self._info["push"] = self._zeros(self.n_worlds, 6)
+        if hi > 0:
+            self.friction = self._info["friction"] = self._zeros(self.n_worlds).fill_(float(ground_mu))
+        rc = N.MwFloatRandConfig(push_interval, push_steps, push_force, push_torque, lo, hi)
+        N.check(N.lib().mw_floatenv_randomize(self._h, ctypes.byref(rc), _ptr(self.push), _ptr(self.friction)),
+                "mw_floatenv_randomize")
+
+    def _setup_inertia(self, mass_scale_range, payload_range, payload_box):
         self.inertial = self.inertia_draws = None
-        if mass_scale_range is not None or payload_range is not None:
-            slo, shi = (0.0, 0.0) if mass_scale_range is None else mass_scale_range
-            plo, phi = (0.0, 0.0) if payload_range is None else payload_range
-            if len(payload_box) != 3:
-                raise ValueError("payload_box must hold three half extents (m)")
-            if shi > 0 or phi > 0:
-                nominal = np.stack([sim.link_params(k - 1, [0])[0] for k in range(n + 1)])
-                self.inertial = self._info["inertial"] = torch.from_numpy(
-                    np.ascontiguousarray(np.broadcast_to(nominal, (n_worlds, n + 1, 10)))).to(self.device)
-                self.inertia_draws = self._info["inertia_draws"] = torch.zeros((n_worlds, n + 5), **f32)
-                self.inertia_draws[:, :n + 1] = 1.0
-            ic = N.MwFloatInertiaConfig(slo, shi, plo, phi, (ctypes.c_float * 3)(*[float(b) for b in payload_box]))
-            ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-            N.check(N.lib().mw_floatenv_inertia(h, ctypes.byref(ic), ptr(self.inertial), ptr(self.inertia_draws)),
-                    "mw_floatenv_inertia")
+        if mass_scale_range is None and payload_range is None:
+            return
+        sim, n, n_worlds = self.sim, self.action_dim, self.n_worlds
+        slo, shi = (0.0, 0.0) if mass_scale_range is None else mass_scale_range
+        plo, phi = (0.0, 0.0) if payload_range is None else payload_range
+        if len(payload_box) != 3:
+            raise ValueError("payload_box must hold three half extents (m)")
+        if shi > 0 or phi > 0:
+            nominal = np.stack([sim.link_params(k - 1, [0])[0] for k in range(n + 1)])
+            self.inertial = self._info["inertial"] = _torch().from_numpy(
+                np.ascontiguousarray(np.broadcast_to(nominal, (n_worlds, n + 1, 10)))).to(self.device)
+            self.inertia_draws = self._info["inertia_draws"] = self._zeros(n_worlds, n + 5)
+            self.inertia_draws[:, :n + 1] = 1.0
+        ic = N.MwFloatInertiaConfig(slo, shi, plo, phi, (ctypes.c_float * 3)(*[float(b) for b in payload_box]))
+        N.check(N.lib().mw_floatenv_inertia(self._h, ctypes.byref(ic), _ptr(self.inertial), _ptr(self.inertia_draws)),
+                "mw_floatenv_inertia")
 
+    def _setup_joints(self, joint_damping_range, joint_friction_range, effort_scale_range, joint_rand_dofs):
         self.joint_dynamics = self.joint_draws = None
-        if joint_damping_range is not None or joint_friction_range is not None or effort_scale_range is not None:
-            dlo, dhi = (0.0, 0.0) if joint_damping_range is None else joint_damping_range
-            flo, fhi = (0.0, 0.0) if joint_friction_range is None else joint_friction_range
-            elo, ehi = (0.0, 0.0) if effort_scale_range is None else effort_scale_range
-            mask = 0
-            for d in (() if joint_rand_dofs is None else joint_rand_dofs):
-                di = sim.joint_names.index(d) if isinstance(d, str) else int(d)
-                if not 0 <= di < n:
-                    raise ValueError(f"joint_rand_dofs: dof {d!r} out of range [0, {n})")
-                mask |= 1 << di
-            if joint_rand_dofs is not None and mask == 0:
-                raise ValueError("joint_rand_dofs is empty (None = every joint)")
-            if dhi > 0 or fhi > 0 or ehi > 0:
-                nominal = np.stack([sim.joint_dynamics(d, [0])[0] for d in range(n)])
-                self.joint_dynamics = self._info["joint_dynamics"] = torch.from_numpy(
-                    np.tile(nominal, (n_worlds, 1, 1))).to(self.device)
-                self.joint_draws = self._info["joint_draws"] = torch.zeros((n_worlds, n, 3), **f32)
-                self.joint_draws[:, :, 2] = 1.0
-            jc = N.MwFloatJointConfig(dlo, dhi, flo, fhi, elo, ehi, mask)
-            ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-            N.check(N.lib().mw_floatenv_joints(h, ctypes.byref(jc), ptr(self.joint_dynamics), ptr(self.joint_draws)),
-                    "mw_floatenv_joints")
+        if joint_damping_range is None and joint_friction_range is None and effort_scale_range is None:
+            return
+        sim, n, n_worlds = self.sim, self.action_dim, self.n_worlds
+        dlo, dhi = (0.0, 0.0) if joint_damping_range is None else joint_damping_range
+        flo, fhi = (0.0, 0.0) if joint_friction_range is None else joint_friction_range
+        elo, ehi = (0.0, 0.0) if effort_scale_range is None else effort_scale_range
+        mask = 0
+        for d in (() if joint_rand_dofs is None else joint_rand_dofs):
+            di = sim.joint_names.index(d) if isinstance(d, str) else int(d)
+            if not 0 <= di < n:
+                raise ValueError(f"joint_rand_dofs: dof {d!r} out of range [0, {n})")
+            mask |= 1 << di
+        if joint_rand_dofs is not None and mask == 0:
+            raise ValueError("joint_rand_dofs is empty (None = every joint)")
+        if dhi > 0 or fhi > 0 or ehi > 0:
+            nominal = np.stack([sim.joint_dynamics(d, [0])[0] for d in range(n)])
+            self.joint_dynamics = self._info["joint_dynamics"] = _torch().from_numpy(
+                np.tile(nominal, (n_worlds, 1, 1))).to(self.device)
+            self.joint_draws = self._info["joint_draws"] = self._zeros(n_worlds, n, 3)
+            self.joint_draws[:, :, 2] = 1.0
+        jc = N.MwFloatJointConfig(dlo, dhi, flo, fhi, elo, ehi, mask)
+        N.check(N.lib().mw_floatenv_joints(self._h, ctypes.byref(jc), _ptr(self.joint_dynamics),
+                                           _ptr(self.joint_draws)), "mw_floatenv_joints")
 
+    def _setup_noise(self, obs_noise, action_delay_range):
         self.obs_noise = self.clean_obs = self.clean_terminal_obs = self.action_delay = None
-        if obs_noise is not None or action_delay_range is not None:
-            amp = None
-            if obs_noise is not None:
-                amp = self._noise_vector(obs_noise)
-                self.obs_noise = torch.from_numpy(amp).to(self.device)
-                self.clean_obs = self._info["clean_obs"] = torch.zeros((n_worlds, self.obs_dim), **f32)
-                self.clean_terminal_obs = self._info["clean_terminal_obs"] = torch.zeros((n_worlds, self.obs_dim), **f32)
-            lo, hi = (0, 0) if action_delay_range is None else action_delay_range
-            if int(lo) != lo or int(hi) != hi:
-                raise ValueError("action_delay_range must hold two whole numbers of control steps")
-            if action_delay_range is not None:
-                self.action_delay = self._info["action_delay"] = torch.zeros((n_worlds,), dtype=torch.int32,
-                                                                              device=self.device)
-            nc = N.MwFloatNoiseConfig(int(lo), int(hi))
-            ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-            N.check(N.lib().mw_floatenv_noise(
-                h, ctypes.byref(nc), None if amp is None else amp.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
-                ptr(self.clean_obs), ptr(self.clean_terminal_obs), ptr(self.action_delay)), "mw_floatenv_noise")
+        if obs_noise is None and action_delay_range is None:
+            return
+        torch = _torch()
+        amp = None
+        if obs_noise is not None:
+            amp = self._noise_vector(obs_noise)
+            self.obs_noise = torch.from_numpy(amp).to(self.device)
+            self.clean_obs = self._info["clean_obs"] = self._zeros(self.n_worlds, self.obs_dim)
+            self.clean_terminal_obs = self._info["clean_terminal_obs"] = self._zeros(self.n_worlds, self.obs_dim)
+        lo, hi = (0, 0) if action_delay_range is None else action_delay_range
+        if int(lo) != lo or int(hi) != hi:
+            raise ValueError("action_delay_range must hold two whole numbers of control steps")
+        if action_delay_range is not None:
+            self.action_delay = self._info["action_delay"] = self._zeros(self.n_worlds, dtype=torch.int32)
+        nc = N.MwFloatNoiseConfig(int(lo), int(hi))
+        N.check(N.lib().mw_floatenv_noise(
+            self._h, ctypes.byref(nc), None if amp is None else _fptr(amp), _ptr(self.clean_obs),
+            _ptr(self.clean_terminal_obs), _ptr(self.action_delay)), "mw_floatenv_noise")
 
+    def _setup_shaping(self, model_file, reward_terms, termination_links, termination_force, penalised_links,
+                       collision_force_min, base_height_target, soft_limit, stumble_ratio, max_contact_force):
         self.reward_term_names = self.reward_terms = self.torques = None
         self.episode_return = self.episode_length = self.episode_terms = None
         self.termination_links = self.penalised_links = None
-        if reward_terms or termination_links or penalised_links:
-            weights = np.zeros(N.FLOAT_SHAPE_TERMS, np.float32)
-            for name, value in (reward_terms or {}).items():
-                if name not in REWARD_TERMS:
-                    raise ValueError(f"reward_terms: unknown term {name!r}; known: {list(REWARD_TERMS)}")
-                weights[REWARD_TERMS.index(name)] = value
-            self.termination_links = self._resolve_links(model_file, termination_links or (), limit=None)
-            self.penalised_links = self._resolve_links(model_file, penalised_links or ())
-            term = np.ascontiguousarray(self.termination_links, dtype=np.int32)
-            pen = np.ascontiguousarray(self.penalised_links, dtype=np.int32)
-            ip = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if len(a) else None
-            self.reward_term_names = REWARD_TERMS
-            self.reward_terms = torch.zeros((n_worlds, N.FLOAT_SHAPE_TERMS), **f32)
-            self.torques = torch.zeros((n_worlds, n), **f32)
-            self.episode_return = torch.zeros((n_worlds,), **f32)
-            self.episode_length = torch.zeros((n_worlds,), dtype=torch.int32, device=self.device)
-            self.episode_terms = torch.zeros((n_worlds, N.FLOAT_SHAPE_TERMS), **f32)
-            sc = N.MwFloatShapeConfig(
-                (ctypes.c_float * N.FLOAT_SHAPE_TERMS)(*weights.tolist()),
-                float(self.home_base[2]) if base_height_target is None else base_height_target, soft_limit,
-                collision_force_min, stumble_ratio, max_contact_force, termination_force, len(pen), len(term),
-                ip(pen), ip(term))
-            ptr = lambda t: ctypes.c_void_p(t.data_ptr())
-            N.check(N.lib().mw_floatenv_shaping(
-                h, ctypes.byref(sc), ptr(self.reward_terms), ptr(self.torques), ptr(self.episode_return),
-                ptr(self.episode_length), ptr(self.episode_terms)), "mw_floatenv_shaping")
-            self._info.update(reward_terms=self.reward_terms, torques=self.torques,
-                              episode_return=self.episode_return, episode_length=self.episode_length,
-                              episode_terms=self.episode_terms)
+        if not (reward_terms or termination_links or penalised_links):
+            return
+        n_worlds = self.n_worlds
+        weights = np.zeros(N.FLOAT_SHAPE_TERMS, np.float32)
+        for name, value in (reward_terms or {}).items():
+            if name not in REWARD_TERMS:
+                raise ValueError(f"reward_terms: unknown term {name!r}; known: {list(REWARD_TERMS)}")
+            weights[REWARD_TERMS.index(name)] = value
+        self.termination_links = self._resolve_links(model_file, termination_links or (), limit=None)
+        self.penalised_links = self._resolve_links(model_file, penalised_links or ())
+        term = np.ascontiguousarray(self.termination_links, dtype=np.int32)
+        pen = np.ascontiguousarray(self.penalised_links, dtype=np.int32)
+        self.reward_term_names = REWARD_TERMS
+        self.reward_terms = self._zeros(n_worlds, N.FLOAT_SHAPE_TERMS)
+        self.torques = self._zeros(n_worlds, self.action_dim)
+        self.episode_return = self._zeros(n_worlds)
+        self.episode_length = self._zeros(n_worlds, dtype=_torch().int32)
+        self.episode_terms = self._zeros(n_worlds, N.FLOAT_SHAPE_TERMS)
+        sc = N.MwFloatShapeConfig(
+            (ctypes.c_float * N.FLOAT_SHAPE_TERMS)(*weights.tolist()),
+            float(self.home_base[2]) if base_height_target is None else base_height_target, soft_limit,
+            collision_force_min, stumble_ratio, max_contact_force, termination_force, len(pen), len(term),
+            _iptr(pen), _iptr(term))
+        N.check(N.lib().mw_floatenv_shaping(
+            self._h, ctypes.byref(sc), _ptr(self.reward_terms), _ptr(self.torques), _ptr(self.episode_return),
+            _ptr(self.episode_length), _ptr(self.episode_terms)), "mw_floatenv_shaping")
+        self._info.update(reward_terms=self.reward_terms, torques=self.torques,
+                          episode_return=self.episode_return, episode_length=self.episode_length,
+                          episode_terms=self.episode_terms)
 
     def _noise_vector(self, obs_noise) -> np.ndarray:
         """obs_noise (group name -> amplitude, or obs_dim values) as the float32 vector the library takes."""
@@ -550,34 +594,23 @@ class FloatVecEnv:
         """Reset every world (episode 0); returns obs [n_worlds, obs_dim].  The
         simulator shows the reset state at once (a paused run applies it)."""
         self.sim._cache.clear()
-        N.check(N.lib().mw_vecenv_reset(self._h, ctypes.c_void_p(self.obs.data_ptr())), "reset")
+        N.check(N.lib().mw_vecenv_reset(self._h, self._out[0]), "reset")
         return self.obs
 
     def step(self, actions) -> Tuple[object, object, object, Dict]:
         """Asynchronous on the current stream; returns views of reused buffers."""
         self._check_actions(actions)
         self.sim._cache.clear()
-        N.check(N.lib().mw_vecenv_step(
-            self._h, ctypes.c_void_p(actions.data_ptr()), ctypes.c_void_p(self.obs.data_ptr()),
-            ctypes.c_void_p(self.reward.data_ptr()), ctypes.c_void_p(self.done.data_ptr()),
-            ctypes.c_void_p(self.terminal_obs.data_ptr())), "step")
+        N.check(N.lib().mw_vecenv_step(self._h, _ptr(actions), *self._out), "step")
         return self.obs, self.reward, self.done, dict(self._info)
 
     def step_raw(self, actions_ptr: int) -> None:
         """Launch one step with a raw device pointer (bench / graph capture)."""
-        N.check(N.lib().mw_vecenv_step(self._h, ctypes.c_void_p(actions_ptr),
-                                       ctypes.c_void_p(self.obs.data_ptr()),
-                                       ctypes.c_void_p(self.reward.data_ptr()),
-                                       ctypes.c_void_p(self.done.data_ptr()),
-                                       ctypes.c_void_p(self.terminal_obs.data_ptr())), "step")
+        N.check(N.lib().mw_vecenv_step(self._h, ctypes.c_void_p(actions_ptr), *self._out), "step")
 
     def rollout(self, actions):
         """Not available: a floating-base step is three launches, not a fused one."""
-        obs = self.obs
-        N.check(N.lib().mw_vecenv_rollout(
-            self._h, 1, ctypes.c_void_p(actions.data_ptr()), ctypes.c_void_p(obs.data_ptr()),
-            ctypes.c_void_p(self.reward.data_ptr()), ctypes.c_void_p(self.done.data_ptr()),
-            ctypes.c_void_p(self.terminal_obs.data_ptr())), "rollout")
+        N.check(N.lib().mw_vecenv_rollout(self._h, 1, _ptr(actions), *self._out), "rollout")
 
     def counters(self):
         """(episode, steps) per world as int32 tensors (copies of the uint32 counters)."""

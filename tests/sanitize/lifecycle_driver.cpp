@@ -1,6 +1,6 @@
 // lifecycle_driver.cpp -- what the handles of the C ABI own, under ASan/UBSan.
 //
-// Links the host layer (sim.cpp, world_params.cpp, vecenv.cpp, scene.cpp, model.cpp, mesh.cpp)
+// Links the host layer (sim.cpp, world_params.cpp, vecenv.cpp, floatenv.cpp, scene.cpp, model.cpp, mesh.cpp)
 // against hip_standin.cpp instead of the HIP runtime.  Every scenario runs
 // once cleanly, then once for each k = 0, 1, ... with the k-th creating call
 // (buffer, stream, event) failing, until a run no longer reaches its k-th

@@ -15,6 +15,7 @@ import subprocess
 import pytest
 
 from conftest import ROOT
+from host_build import build_host, fp as _fp, host_sim as _host_sim
 
 FIELDS = ["damping_lo", "damping_hi", "friction_lo", "friction_hi", "effort_scale_lo", "effort_scale_hi", "dof_mask"]
 SYMBOLS = ["mw_set_joint_dynamics", "mw_joint_dynamics", "mw_floatenv_joints"]
@@ -99,43 +100,13 @@ def test_python_layer_carries_the_arguments():
 
 
 # ---- the argument checks and the host-side rules, through a host build ----
-# The library's host layer (sim.cpp, world_params.cpp, vecenv.cpp, scene.cpp, model.cpp, mesh.cpp)
-# over tests/sanitize/hip_standin.cpp, the stand-in for the HIP runtime that the
-# sanitizer lifecycle driver uses (plain g++, no sanitizer): device memory is
-# host memory and the kernel launchers do nothing, so everything the host decides
-# -- validation, the mirror, the shared setter, ownership -- runs without a GPU.
+# host_build.py: the library's host layer over the stand-in for the HIP runtime,
+# so everything the host decides -- validation, the mirror, the shared setter,
+# ownership -- runs without a GPU.
 
 @pytest.fixture(scope="module")
 def host(N, tmp_path_factory):
-    csrc = os.path.join(ROOT, "gym-ignition_amd", "csrc")
-    out = str(tmp_path_factory.mktemp("hostlib") / "libmwhost.so")
-    rocm = os.environ.get("ROCM_PATH", "/opt/rocm")
-    srcs = [os.path.join(csrc, f) for f in ("sim.cpp", "world_params.cpp", "vecenv.cpp", "scene.cpp", "model.cpp",
-                                                "mesh.cpp")]
-    subprocess.run(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-w", "-D__HIP_PLATFORM_AMD__",
-                    "-I", os.path.join(rocm, "include"), "-I", os.path.join(ROOT, "include"), "-I", csrc,
-                    os.path.join(ROOT, "tests", "sanitize", "hip_standin.cpp"), *srcs, "-o", out], check=True)
-    L = ctypes.CDLL(out)
-    for name, res, args in N.SIGNATURES:
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = res, args
-    return L
-
-
-def _host_sim(N, L, model, W):
-    import numpy as np
-    from mwstep import get_model_file
-    sim = ctypes.c_void_p()
-    mc = N.MwConfig(1e-3, 1.0, 1, W, 0, 20)
-    assert L.mw_create(ctypes.byref(mc), ctypes.byref(sim)) == N.MW_OK
-    pose = np.float64([0, 0, 0.45, 1, 0, 0, 0])
-    assert L.mw_load_model(sim, get_model_file(model).encode(), N.dptr(pose), b"") == N.MW_OK, L.mw_last_error()
-    assert L.mw_initialize(sim) == N.MW_OK, L.mw_last_error()
-    return sim
-
-
-def _fp(a):
-    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+    return build_host(N, tmp_path_factory.mktemp("hostlib"))
 
 
 def _all_words(N, L, sim, W, n):

@@ -15,85 +15,13 @@ the per-link contact force sums (another summation order) within
 
 import ctypes
 import math
-import os
 
 import numpy as np
 import pytest
 
+from float_env_harness import QUAD_GAINS, STAND, _captured_step_graph, _check_obs, _make, _reset_twin, _twin, _unif32
+
 pytestmark = pytest.mark.gpu
-
-STAND = [0.6, -1.2] * 4
-QUAD_GAINS = [[400.0, 0.0, 10.0, -60.0, 60.0, 0.0, 0.0, -1.0]] * 8
-
-
-def _twin(env, model, gains=None):
-    """A host-commanded Simulator configured as the env's."""
-    from mwstep import get_model_file
-    from mwstep import native as N
-    from mwstep.sim import Simulator
-    s = env.sim
-    if not (model.lstrip().startswith("<") or os.path.exists(model)):      # else: a URDF text or file
-        model = get_model_file(model)
-    twin = Simulator(model, n_worlds=env.n_worlds, step_size=s.step_size,
-                     steps_per_run=s.steps_per_run, pgs_iters=env._pgs_iters, pose=tuple(env.home_base.tolist()))
-    twin.set_ground_plane(True, 1.0)
-    twin.enable_contacts(True)
-    for d, g in enumerate(gains or []):
-        twin.set_pid(d, g)
-    if env.action_mode == "position":
-        twin.set_controller_period(s.step_size)
-        twin.set_control_mode(N.MODE_POSITION)
-    else:
-        twin.set_control_mode(N.MODE_FORCE)
-    return twin
-
-
-def _reset_twin(twin, obs, worlds=None):
-    """Reset worlds of the twin through the host setters with the values of the env's obs rows."""
-    n = twin.dofs
-    if worlds is None:
-        twin.set("reset_q", obs[:, 13:13 + n].astype(np.float64))
-        twin.set("reset_qd", obs[:, 13 + n:13 + 2 * n].astype(np.float64))
-        twin.reset_base_pose(obs[:, :7].astype(np.float64))
-        twin.reset_base_velocity(obs[:, 7:13].astype(np.float64))
-        return
-    for w in worlds:
-        twin.set("reset_q", obs[w:w + 1, 13:13 + n].astype(np.float64), w0=w, nw=1)
-        twin.set("reset_qd", obs[w:w + 1, 13 + n:13 + 2 * n].astype(np.float64), w0=w, nw=1)
-        twin.reset_base_pose(obs[w, :7].astype(np.float64), w0=w, nw=1)
-        twin.reset_base_velocity(obs[w, 7:13].astype(np.float64), w0=w, nw=1)
-
-
-def _make(kind, W, **kw):
-    from mwstep import FloatVecEnv
-    env = getattr(FloatVecEnv, kind)(W, **kw)
-    env._pgs_iters = kw.get("pgs_iters", 50 if kind == "icub" else 20)
-    return env
-
-
-def _link_forces(twin, links, w):
-    c, b = twin.contacts(w), twin.contact_bodies(w)
-    return np.array([c[b == link, 8].sum() for link in links])
-
-
-def _check_obs(obs, twin, links, worlds=None):
-    """obs rows against the twin's getters (after the same step)."""
-    n = twin.dofs
-    ws = np.arange(twin.n_worlds) if worlds is None else np.asarray(worlds)
-    np.testing.assert_array_equal(obs[ws, :7], twin.base_pose()[ws].astype(np.float32))
-    np.testing.assert_array_equal(obs[ws, 13:13 + n], twin.get("q")[ws].astype(np.float32))
-    np.testing.assert_array_equal(obs[ws, 13 + n:13 + 2 * n], twin.get("qd")[ws].astype(np.float32))
-    v = twin.base_velocity()[ws]
-    err_v = float((np.abs(obs[ws, 7:13] - v) / np.maximum(1.0, np.abs(v))).max())
-    f = np.array([_link_forces(twin, links, w) for w in ws])
-    got = obs[ws, 13 + 2 * n:]
-    err_f = float((np.abs(got - f) / np.maximum(1.0, np.abs(f))).max()) if len(links) else 0.0
-    return err_v, err_f
-
-
-def _unif32(x, lo, hi):
-    t = np.float32((x >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0))
-    return np.float32(lo) + (np.float32(hi) - np.float32(lo)) * t
 
 
 def _reset_ref(oracle, sim, home, noise, seed, world, episode):
@@ -349,45 +277,6 @@ def test_divergence_resets_the_world(require_gpu):
     assert count == 1 and not flags.any()
     env.close()
     twin.close()
-
-
-def _loaded_hip():
-    """The HIP runtime this process already uses."""
-    for line in open("/proc/self/maps"):
-        if "libamdhip64" in line:
-            return ctypes.CDLL(line.split()[-1])
-    raise RuntimeError("the HIP runtime is not loaded")
-
-
-def _captured_step_graph(env, actions):
-    """Capture one env.step into a HIP graph (never launched): its node types and edges."""
-    import torch
-    hip = _loaded_hip()
-    vp = ctypes.c_void_p
-    stream = vp(torch.cuda.current_stream(env.device).cuda_stream)
-    graph = vp()
-    assert hip.hipStreamBeginCapture(stream, 2) == 0      # relaxed mode
-    try:
-        env.step_raw(actions.data_ptr())
-    finally:
-        rc = hip.hipStreamEndCapture(stream, ctypes.byref(graph))
-    assert rc == 0 and graph.value
-    n = ctypes.c_size_t()
-    assert hip.hipGraphGetNodes(graph, None, ctypes.byref(n)) == 0
-    nodes = (vp * n.value)()
-    assert hip.hipGraphGetNodes(graph, nodes, ctypes.byref(n)) == 0
-    types = []
-    for node in nodes:
-        t = ctypes.c_int()
-        assert hip.hipGraphNodeGetType(vp(node), ctypes.byref(t)) == 0
-        types.append(t.value)
-    m = ctypes.c_size_t()
-    assert hip.hipGraphGetEdges(graph, None, None, ctypes.byref(m)) == 0
-    src, dst = (vp * m.value)(), (vp * m.value)()
-    assert hip.hipGraphGetEdges(graph, src, dst, ctypes.byref(m)) == 0
-    edges = [(list(nodes).index(a), list(nodes).index(b)) for a, b in zip(src, dst)]
-    hip.hipGraphDestroy(graph)
-    return types, edges
 
 
 def test_graph_capture(require_gpu):

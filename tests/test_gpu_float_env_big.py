@@ -13,23 +13,18 @@ mw_get_state record; the draws are restated from the oracle's Philox; the
 shaping terms are the host build's bits.
 """
 
-import math
-
 import numpy as np
 import pytest
 
 import big_tree_cases as C
+from float_env_harness import (ALL, FREE, JOINTS, PUSH, _captured_step_graph, _check_draws, _check_obs, _check_rows,
+                               _delay_ref, _dev, _forces32, _limits, _nominal, _params, _parity, _reset_twin, _twin)
+from float_joints_ref import build_harness
 from float_shape_ref import ShapeHost
-from test_gpu_float_env import _captured_step_graph, _check_obs, _reset_twin, _twin
-from test_gpu_float_joints_env import JOINTS, _check_draws, _nominal, _parity, fj  # noqa: F401
-from test_gpu_float_noise import _check_rows, _delay_ref
-from test_gpu_float_shape import ALL, _forces32, _limits, _params
 
 pytestmark = pytest.mark.gpu
 
 NAME, N = "tree48", 48
-FREE = dict(z_min=-10.0, max_tilt=math.pi)
-PUSH = dict(push_interval=7, push_steps=2, push_force=30.0, push_torque=5.0)
 LOCO = dict(task="locomotion", command_ranges=((-1.0, 1.0), (-0.5, 0.5), (-1.0, 1.0)), cmd_interval=3,
             cmd_zero_prob=0.2, cmd_min=0.1, w_action_rate=0.01)
 SCALES, PAYLOADS, BOX = (0.8, 1.25), (0.0, 5.0), (0.1, 0.08, 0.05)
@@ -50,6 +45,11 @@ def home(oracle):
 
 
 @pytest.fixture(scope="module")
+def fj(tmp_path_factory):
+    return build_harness(tmp_path_factory.mktemp("fj_big"))
+
+
+@pytest.fixture(scope="module")
 def fs(tmp_path_factory):
     return ShapeHost(tmp_path_factory.mktemp("fs_big"))
 
@@ -65,11 +65,6 @@ def _env(home, n_worlds, action_mode="position", **kw):
     assert env.sim.float_kernel() == 2 and env.sim.dofs == N > 32 and env.action_dim == N
     assert len(env.contact_links) == 8
     return env
-
-
-def _dev(env, a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(env.device)
 
 
 def _check_layout(env, loco):
@@ -187,7 +182,7 @@ def test_twin_parity_with_everything_on(require_gpu, home, mode, n_worlds):
     penalised links), observation noise, action delay, pushes, ground friction,
     mass scales with a payload and joint draws on the dofs 32..47: the dynamic
     LDS of the post kernel at the maximum its launcher computes.  The launch
-    succeeds, and test_gpu_float_joints_env._parity holds over two episodes."""
+    succeeds, and float_env_harness._parity holds over two episodes."""
     import torch
     position = mode == "position"
     steps, H = 16, 8
@@ -197,7 +192,8 @@ def test_twin_parity_with_everything_on(require_gpu, home, mode, n_worlds):
     assert env.reward_terms.shape == (n_worlds, 10) and env.action_delay.shape == (n_worlds,)
     twin = _twin(env, C.urdf(NAME), [C.ENV_PID] * N if position else None)
     acts = _actions(steps, n_worlds, position, 5)
-    seen = _parity(_CleanRows(env), twin, lambda k: acts[k], steps, H, _command_of(env, position, 0.5))
+    seen = _parity(_CleanRows(env), twin, lambda k: acts[k], steps, H, _command_of(env, position, 0.5),
+                   carry=("inertial", "joint_dynamics"))["joint_dynamics"]
     torch.cuda.synchronize()
     assert len(seen) == 3 and not np.array_equal(seen[0], seen[1])
     low = [d for d in range(N) if d not in HIGH_DOFS]
@@ -213,7 +209,7 @@ def test_twin_parity_with_everything_on(require_gpu, home, mode, n_worlds):
     twin.close()
 
 
-def test_draws_are_the_stated_ones(require_gpu, oracle, home, fj):  # noqa: F811
+def test_draws_are_the_stated_ones(require_gpu, oracle, home, fj):
     """W = 65, every world of the tile edge, episodes 0 and 1:
       * the 49 link scales (the 13th Philox block holds the last link's alone),
         the payload and its position;
@@ -328,7 +324,7 @@ def test_noise_vector_edges(require_gpu, oracle, home):
     env.close()
 
 
-def test_joint_mask_of_high_dofs_only(require_gpu, oracle, home, fj):  # noqa: F811
+def test_joint_mask_of_high_dofs_only(require_gpu, oracle, home, fj):
     """dof_mask = bits 32..47: those joints draw, the other 32 keep the nominal
     words bit for bit (asserted by _check_draws) and report the draws 0, 0, 1."""
     n_worlds, seed = 65, 24

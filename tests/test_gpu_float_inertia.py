@@ -15,37 +15,9 @@ mw_link_params: the WPAR instances of the world-per-wavefront kernel).
 import numpy as np
 import pytest
 
+from float_env_harness import _quadruped, _run_quadruped
+
 pytestmark = pytest.mark.gpu
-
-STAND = [0.6, -1.2] * 4
-
-
-def _quadruped(W):
-    from mwstep import get_model_file
-    from mwstep import native as N
-    from mwstep.sim import Simulator
-    sim = Simulator(get_model_file("quadruped"), n_worlds=W, pose=(0, 0, 0.43, 1, 0, 0, 0))
-    assert sim.float_kernel() == 2
-    sim.set_ground_plane(True, 1.0)
-    sim.enable_contacts(True)
-    sim.set_control_mode(N.MODE_FORCE)
-    return sim
-
-
-def _run_quadruped(sim, torques, worlds=None, watch=None):
-    """The stand posture 1 cm lower than where it stands on the shanks' spheres
-    (z = 0.44), so the feet are in contact from the first step; then one
-    run per row of torques [steps, W, 8].  watch: a list that receives, per
-    step, how many of worlds 0, W // 2, W - 1 have contact points."""
-    W = sim.n_worlds
-    sim.set("reset_q", np.tile(np.float64(STAND), (W, 1)))
-    sim.run(paused=True)
-    for tau in torques:
-        sim.set("force_target", tau if worlds is None else tau[worlds])
-        sim.run()
-        if watch is not None:
-            watch.append(sum(len(sim.contacts(w)) > 0 for w in (0, W // 2, W - 1)))
-    return sim.get_state()
 
 
 def _set_all_to_nominal(sim):

@@ -12,71 +12,17 @@ from the reported draws within the derived bound of
 tests/host_float_inertia/harness.cpp."""
 
 import ctypes
-import math
 
 import numpy as np
 import pytest
 
+from float_env_harness import FREE, LOCO, PUSH, STAND, _captured_step_graph, _make, _parity, _twin
 from float_inertia_ref import PAYLOAD, SCALE, apply_ref, build_harness, draw_ref, harness_apply, inertia_about_com
-from test_gpu_float_env import STAND, _make, _reset_twin, _twin
 
 pytestmark = pytest.mark.gpu
 
-FREE = dict(z_min=-10.0, max_tilt=math.pi)           # no termination by height or tilt
-PUSH = dict(push_interval=7, push_steps=2, push_force=30.0, push_torque=5.0)
-LOCO = dict(task="locomotion", command_ranges=((-1.0, 1.0), (-0.5, 0.5), (-1.0, 1.0)), cmd_interval=3,
-            cmd_zero_prob=0.2, w_action_rate=0.01)
 SCALES, PAYLOADS, BOX = (0.5, 2.0), (0.0, 10.0), (0.1, 0.08, 0.05)
 INERTIA = dict(mass_scale_range=SCALES, payload_range=PAYLOADS, payload_box=BOX)
-
-
-def _set_twin_inertial(twin, inertial, worlds=None):
-    for link in range(-1, twin.dofs):
-        words = inertial[:, link + 1]
-        twin.set_link_params(link, words if worlds is None else words[worlds], worlds)
-
-
-def _parity(env, twin, actions_of, steps, H, command_of):
-    """env (every randomisation and the locomotion task on) and twin in
-    lockstep; the twin is given the reported wrench of every step and, at every
-    reset, the reported inertial words, friction and reset state."""
-    import torch
-    W = env.n_worlds
-    obs = env.reset().cpu().numpy()
-    inertial = env.inertial.cpu().numpy()
-    _set_twin_inertial(twin, inertial)
-    twin.set_ground_friction(env.friction.cpu().numpy().astype(np.float64))
-    _reset_twin(twin, obs)
-    twin.run(paused=True)
-    np.testing.assert_array_equal(env.sim.get_state(), twin.get_state())
-    duration = env.sim.steps_per_run * env.sim.step_size
-    n_done = 0
-    seen = [inertial.copy()]
-    for k in range(1, steps + 1):
-        a = actions_of(k)
-        o, _, d, info = env.step(torch.from_numpy(a).to(env.device))
-        d = d.cpu().numpy().astype(bool)
-        twin.apply_world_wrench(-1, info["push"].cpu().numpy().astype(np.float64), duration)
-        command_of(twin, a)
-        twin.run()
-        np.testing.assert_array_equal(env.sim.get_state(), twin.get_state(), err_msg=f"state after step {k}")
-        assert d.all() == (k % H == 0) and d.any() == (k % H == 0)
-        new = info["inertial"].cpu().numpy()
-        assert info["inertial"] is env.inertial
-        # the words change where, and only where, an episode ended
-        np.testing.assert_array_equal((new != inertial).any(axis=(1, 2)), d, err_msg=f"inertial changes at step {k}")
-        if d.any():
-            n_done += 1
-            inertial = new
-            seen.append(new.copy())
-            done = np.flatnonzero(d)
-            _set_twin_inertial(twin, inertial, done)
-            twin.set_ground_friction(info["friction"].cpu().numpy().astype(np.float64))
-            _reset_twin(twin, o.cpu().numpy(), done)
-        for link in (-1, twin.dofs - 1):
-            np.testing.assert_array_equal(env.sim.link_params(link), inertial[:, link + 1])
-    assert n_done == steps // H
-    return seen
 
 
 def test_twin_parity_torque_quadruped(require_gpu):
@@ -91,7 +37,8 @@ def test_twin_parity_torque_quadruped(require_gpu):
     rng = np.random.default_rng(3)
     acts = rng.uniform(-5, 5, (steps + 1, W, 8)).astype(np.float32)
     seen = _parity(env, twin, lambda k: acts[k], steps, H,
-                   lambda t, a: t.set("force_target", (np.float32(0.5) * a).astype(np.float64)))
+                   lambda t, a: t.set("force_target", (np.float32(0.5) * a).astype(np.float64)),
+                   carry=("inertial",))["inertial"]
     masses = np.stack([s[:, :, 0] for s in seen])                     # [episodes, W, links]
     nominal = twin.link_params(0, [0])[0, 0]
     print(f"quadruped: {len(seen)} episodes, thigh mass {masses[:, :, 1].min():.3f} .. {masses[:, :, 1].max():.3f} "
@@ -114,7 +61,8 @@ def test_twin_parity_position_icub(require_gpu):
     rng = np.random.default_rng(5)
     acts = rng.uniform(-0.4, 0.4, (steps + 1, W, 32)).astype(np.float32)
     seen = _parity(env, twin, lambda k: acts[k], steps, H,
-                   lambda t, a: t.set("position_target", env.sim.get("position_target")))
+                   lambda t, a: t.set("position_target", env.sim.get("position_target")),
+                   carry=("inertial",))["inertial"]
     assert len(seen) == 4 and not np.array_equal(seen[0], seen[1])
     env.close()
     twin.close()
@@ -301,7 +249,6 @@ def test_graph_capture_with_inertia(require_gpu):
             np.testing.assert_array_equal(env.obs.cpu().numpy(), plain.obs.cpu().numpy())
             np.testing.assert_array_equal(env.inertial.cpu().numpy(), plain.inertial.cpu().numpy())
             n_done += int(env.done.sum())
-        from test_gpu_float_env import _captured_step_graph
         types, _ = _captured_step_graph(env, a)
         side.synchronize()
     assert types == [0, 0, 0], types                 # the step stays three kernel nodes

@@ -19,8 +19,8 @@ the WPAR instances of the world-per-wavefront kernel read).
 import numpy as np
 import pytest
 
+from float_env_harness import _quadruped, _run_quadruped
 from float_joints_ref import FLT_MAX, write_two_body
-from test_gpu_float_inertia import _quadruped, _run_quadruped
 
 pytestmark = pytest.mark.gpu
 

@@ -12,23 +12,17 @@ three words from the reported draws bit for bit by the host build of the
 kernel's word function (tests/host_float_joints/harness.cpp)."""
 
 import ctypes
-import math
 
 import numpy as np
 import pytest
 
-from float_joints_ref import DAMPING, EFFORT, FRICTION, build_harness, draw_ref, harness_apply
-from test_gpu_float_env import STAND, _make, _reset_twin, _twin
+from float_env_harness import (FREE, JOINTS, LOCO, PUSH, STAND, _captured_step_graph, _check_draws, _make, _nominal,
+                               _parity, _twin)
+from float_joints_ref import build_harness
 
 pytestmark = pytest.mark.gpu
 
-FREE = dict(z_min=-10.0, max_tilt=math.pi)           # no termination by height or tilt
-PUSH = dict(push_interval=7, push_steps=2, push_force=30.0, push_torque=5.0)
-LOCO = dict(task="locomotion", command_ranges=((-1.0, 1.0), (-0.5, 0.5), (-1.0, 1.0)), cmd_interval=3,
-            cmd_zero_prob=0.2, w_action_rate=0.01)
 INERTIA = dict(mass_scale_range=(0.8, 1.25), payload_range=(0.0, 5.0), payload_box=(0.1, 0.08, 0.05))
-DAMP, FRIC, EFF = (0.0, 0.5), (0.0, 2.0), (0.1, 1.0)
-JOINTS = dict(joint_damping_range=DAMP, joint_friction_range=FRIC, effort_scale_range=EFF)
 ICUB_LEGS = [f"{s}_{j}" for s in ("l", "r")
              for j in ("hip_pitch", "hip_roll", "hip_yaw", "knee", "ankle_pitch", "ankle_roll")]
 
@@ -36,38 +30,6 @@ ICUB_LEGS = [f"{s}_{j}" for s in ("l", "r")
 @pytest.fixture(scope="module")
 def fj(tmp_path_factory):
     return build_harness(tmp_path_factory.mktemp("fj"))
-
-
-def _nominal(sim):
-    return np.stack([sim.joint_dynamics(d, [0])[0] for d in range(sim.dofs)])
-
-
-def _check_draws(env, oracle, fj, seed, episode, dofs, nominal, worlds, offset=0):
-    """env.joint_draws against the restatement, env.joint_dynamics against the
-    host build of the kernel's code on those draws; returns the worst draw
-    error over its bound."""
-    n = env.action_dim
-    draws, words = env.joint_draws.cpu().numpy(), env.joint_dynamics.cpu().numpy()
-    assert draws.shape == words.shape == (env.n_worlds, n, 3)
-    sel = list(range(n)) if dofs is None else list(dofs)
-    rest = [d for d in range(n) if d not in sel]
-    # masked-out joints: draws 0, 0, 1 and the nominal words
-    np.testing.assert_array_equal(draws[:, rest], np.tile(np.float32([0.0, 0.0, 1.0]), (env.n_worlds, len(rest), 1)))
-    np.testing.assert_array_equal(words[:, rest], np.tile(nominal[rest], (env.n_worlds, 1, 1)))
-    tol = np.array([4 * 2.0 ** -23 * (r[1] - r[0]) for r in (DAMP, FRIC, EFF)])
-    for e, r in enumerate((DAMP, FRIC, EFF)):
-        assert r[0] - tol[e] <= draws[:, sel, e].min() and draws[:, sel, e].max() <= r[1] + tol[e]
-    worst = 0.0
-    for w in worlds:
-        ref = draw_ref(oracle, seed, offset + w, episode, n, DAMP, FRIC, EFF, dofs)
-        worst = max(worst, float((np.abs(draws[w].astype(np.float64) - ref) / tol).max()))
-    assert worst <= 1.0, worst
-    # the words from the reported draws: the kernel's code on the host, bit for bit
-    want = harness_apply(fj, DAMPING | FRICTION | EFFORT, np.tile(nominal, (env.n_worlds, 1, 1)), draws)
-    np.testing.assert_array_equal(words, want)
-    for d in (sel[0], sel[-1]) + ((rest[0],) if rest else ()):
-        np.testing.assert_array_equal(env.sim.joint_dynamics(d), words[:, d])
-    return worst
 
 
 @pytest.mark.parametrize("W", [1, 63, 65, 130])
@@ -133,54 +95,6 @@ def test_sharding(require_gpu):
     part.close()
 
 
-def _set_twin(twin, env, worlds=None):
-    inertial, joints = env.inertial.cpu().numpy(), env.joint_dynamics.cpu().numpy()
-    for link in range(-1, twin.dofs):
-        words = inertial[:, link + 1]
-        twin.set_link_params(link, words if worlds is None else words[worlds], worlds)
-    for d in range(twin.dofs):
-        words = joints[:, d]
-        twin.set_joint_dynamics(d, words if worlds is None else words[worlds], worlds)
-
-
-def _parity(env, twin, actions_of, steps, H, command_of):
-    """env (every randomisation and the locomotion task on) and twin in
-    lockstep; the twin is given the reported wrench of every step and, at every
-    reset, the reported inertial and joint words, friction and reset state."""
-    import torch
-    obs = env.reset().cpu().numpy()
-    _set_twin(twin, env)
-    twin.set_ground_friction(env.friction.cpu().numpy().astype(np.float64))
-    _reset_twin(twin, obs)
-    twin.run(paused=True)
-    np.testing.assert_array_equal(env.sim.get_state(), twin.get_state())
-    duration = env.sim.steps_per_run * env.sim.step_size
-    joints = env.joint_dynamics.cpu().numpy().copy()
-    seen = [joints]
-    for k in range(1, steps + 1):
-        a = actions_of(k)
-        o, _, d, info = env.step(torch.from_numpy(a).to(env.device))
-        d = d.cpu().numpy().astype(bool)
-        twin.apply_world_wrench(-1, info["push"].cpu().numpy().astype(np.float64), duration)
-        command_of(twin, a)
-        twin.run()
-        np.testing.assert_array_equal(env.sim.get_state(), twin.get_state(), err_msg=f"state after step {k}")
-        assert d.all() == (k % H == 0) and d.any() == (k % H == 0)
-        new = info["joint_dynamics"].cpu().numpy()
-        # the words change where, and only where, an episode ended
-        np.testing.assert_array_equal((new != joints).any(axis=(1, 2)), d, err_msg=f"joint words change at step {k}")
-        if d.any():
-            joints = new.copy()
-            seen.append(joints)
-            done = np.flatnonzero(d)
-            _set_twin(twin, env, done)
-            twin.set_ground_friction(info["friction"].cpu().numpy().astype(np.float64))
-            _reset_twin(twin, o.cpu().numpy(), done)
-    assert len(seen) == 1 + steps // H
-    assert env.sim.constraint_overflow() == twin.constraint_overflow()
-    return seen
-
-
 def test_twin_parity_torque_quadruped(require_gpu):
     """W = 70: two tiles of the env kernels, the second partial; episodes of 7
     steps, so the draws of every world's resets interleave with the run."""
@@ -194,7 +108,8 @@ def test_twin_parity_torque_quadruped(require_gpu):
     rng = np.random.default_rng(3)
     acts = rng.uniform(-40, 40, (steps + 1, W, 8)).astype(np.float32)       # 0.5 a reaches past most effort limits
     seen = _parity(env, twin, lambda k: acts[k], steps, H,
-                   lambda t, a: t.set("force_target", (np.float32(0.5) * a).astype(np.float64)))
+                   lambda t, a: t.set("force_target", (np.float32(0.5) * a).astype(np.float64)),
+                   carry=("inertial", "joint_dynamics"))["joint_dynamics"]
     eff = np.stack([s[:, :, 2] for s in seen])
     print(f"quadruped: {len(seen)} episodes, effort limit {eff.min():.2f} .. {eff.max():.2f} N m")
     assert len(np.unique(eff)) > 0.9 * eff.size                                # differ across worlds and episodes
@@ -215,7 +130,8 @@ def test_twin_parity_position_icub(require_gpu):
     rng = np.random.default_rng(5)
     acts = rng.uniform(-0.4, 0.4, (steps + 1, W, 32)).astype(np.float32)
     seen = _parity(env, twin, lambda k: acts[k], steps, H,
-                   lambda t, a: t.set("position_target", env.sim.get("position_target")))
+                   lambda t, a: t.set("position_target", env.sim.get("position_target")),
+                   carry=("inertial", "joint_dynamics"))["joint_dynamics"]
     assert len(seen) == 3 and not np.array_equal(seen[0], seen[1])
     env.close()
     twin.close()
@@ -283,7 +199,6 @@ def test_graph_capture_with_joints(require_gpu):
             np.testing.assert_array_equal(env.obs.cpu().numpy(), plain.obs.cpu().numpy())
             np.testing.assert_array_equal(env.joint_dynamics.cpu().numpy(), plain.joint_dynamics.cpu().numpy())
             n_done += int(env.done.sum())
-        from test_gpu_float_env import _captured_step_graph
         types, _ = _captured_step_graph(env, a)
         side.synchronize()
     assert types == [0, 0, 0], types                 # the step stays three kernel nodes

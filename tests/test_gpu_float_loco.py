@@ -1,5 +1,5 @@
 """The velocity-command locomotion task of the floating-base env
-(mw_floatenv_locomotion, FloatVecEnv(task="locomotion"); the LOCO instances of
+(mw_floatenv_locomotion, FloatVecEnv(task="locomotion"); the LOCO_EVERY_TERM instances of
 csrc/float_env_kernel.hip around the unchanged wave run).
 
 Physics: the yardstick of test_gpu_float_env.py -- a host-commanded twin
@@ -13,93 +13,21 @@ action and the air counters itself, driven by the rows the env returned
 (terminal_obs for finished worlds), at 2^-23 (n + 8) sum_i |term_i| -- the
 terms are a sum of at most n + 8 float32 roundings, expf's error is relative
 to a value of at most its weight.  Commands: restated from the oracle's
-Philox4x32-10 with test_gpu_float_env._unif32, at 4 * 2^-23 (hi - lo) as in
+Philox4x32-10 with float_env_harness._unif32, at 4 * 2^-23 (hi - lo) as in
 test_gpu_float_rand.py (the device may fuse lo + (hi - lo) t); the zero test
 compares an exact float32 and must agree exactly."""
 
 import ctypes
-import math
 
 import numpy as np
 import pytest
 
-from test_gpu_float_env import (STAND, _captured_step_graph, _check_obs, _link_forces, _make, _reset_twin, _twin,
-                                _unif32)
+from float_env_harness import (FREE, LOCO_EVERY_TERM, RANGES, STAND, _captured_step_graph, _check_obs, _link_forces,
+                               _make, _philox, _reset_twin, _RewardRef, _twin, _unif32)
 
 pytestmark = pytest.mark.gpu
 
-FREE = dict(z_min=-10.0, max_tilt=math.pi)           # no termination by height or tilt
 CMD_BLOCK = 0xC0000000
-RANGES = ((-1.0, 1.0), (-0.5, 0.5), (-1.0, 1.0))
-# every reward term on, so that each shows in the restatement
-LOCO = dict(task="locomotion", command_ranges=RANGES, cmd_interval=3, cmd_zero_prob=0.2, cmd_min=0.1,
-            w_action=0.01, w_pose=0.1, w_track_lin=1.0, w_track_yaw=0.5, track_sigma=0.25, w_lin_z=2.0,
-            w_ang_xy=0.05, w_action_rate=0.01, w_air_time=1.0, air_time_target=0.01, contact_force_min=1.0)
-
-
-def _f(x):
-    """The float32 the env holds for a configured value, as fp64."""
-    return float(np.float32(x))
-
-
-class _RewardRef:
-    """fp64 restatement of the locomotion reward with its own previous action and air counters."""
-
-    def __init__(self, env, kw):
-        self.env, self.kw = env, kw
-        self.n, self.sl = env.action_dim, env.obs_slices
-        self.prev = np.zeros((env.n_worlds, self.n))
-        self.air = np.zeros((env.n_worlds, len(env.contact_links)), np.int64)
-        self.cmd = None
-        self.touchdowns = 0          # with air_steps > 0 under a command above cmd_min
-        self.worst = 0.0             # |reward - restatement| / bound
-        self.env_dt = _f(env.sim.steps_per_run * env.sim.step_size)
-
-    def start(self, obs):
-        """The reset observation: its command is the one the first step runs under."""
-        self.cmd = obs[:, self.sl["command"]].astype(np.float64)
-        np.testing.assert_array_equal(obs[:, self.sl["last_action"]], 0.0)
-        np.testing.assert_array_equal(obs[:, self.sl["body_velocity"]], 0.0)
-
-    def step(self, a, obs, term_obs, done, reward):
-        kw, sl, n = self.kw, self.sl, self.n
-        g = lambda name, default=0.0: _f(kw.get(name, default))
-        rows = np.where(done[:, None], term_obs, obs).astype(np.float64)
-        a64 = a.astype(np.float64)
-        z, qx, qy = rows[:, 2], rows[:, 4], rows[:, 5]
-        term = (z < g("z_min")) | (1 - 2 * (qx * qx + qy * qy) < _f(math.cos(kw.get("max_tilt", math.pi))))
-        v, om = rows[:, sl["body_velocity"]][:, :3], rows[:, sl["body_velocity"]][:, 3:]
-        c = self.cmd
-        contact = rows[:, sl["contacts"]] > g("contact_force_min")
-        touchdown = contact & (self.air > 0)
-        pay = np.where(touchdown, self.air * self.env_dt - g("air_time_target"), 0.0).sum(axis=1)
-        fast = c[:, 0] ** 2 + c[:, 1] ** 2 > g("cmd_min") ** 2
-        self.touchdowns += int((touchdown & fast[:, None]).sum())
-        self.air = np.where(contact, 0, self.air + 1)
-        sigma = g("track_sigma", 0.25)
-        terms = np.stack([
-            np.where(term, 0.0, g("alive_bonus", 1.0)),
-            g("w_forward", 1.0) * rows[:, 7],
-            -g("w_action") * (a64 ** 2).sum(axis=1),
-            -g("w_pose") * ((rows[:, 13:13 + n] - self.env.home_q.astype(np.float64)) ** 2).sum(axis=1),
-            g("w_track_lin", 1.0) * np.exp(-((c[:, 0] - v[:, 0]) ** 2 + (c[:, 1] - v[:, 1]) ** 2) / sigma),
-            g("w_track_yaw", 0.5) * np.exp(-((c[:, 2] - om[:, 2]) ** 2) / sigma),
-            -g("w_lin_z") * v[:, 2] ** 2,
-            -g("w_ang_xy") * (om[:, 0] ** 2 + om[:, 1] ** 2),
-            -g("w_action_rate") * ((a64 - self.prev) ** 2).sum(axis=1),
-            np.where(fast, g("w_air_time") * pay, 0.0)], axis=1)
-        bound = 2.0 ** -23 * (n + 8) * np.abs(terms).sum(axis=1)
-        self.worst = max(self.worst, float((np.abs(reward - terms.sum(axis=1)) / bound).max()))
-        # the new words of the rows
-        np.testing.assert_array_equal(rows[:, sl["last_action"]], a64)
-        np.testing.assert_array_equal(obs[done][:, sl["last_action"]], 0.0)
-        w, x, y, zz = rows[:, 3], rows[:, 4], rows[:, 5], rows[:, 6]
-        grav = -np.stack([2 * (x * zz - w * y), 2 * (y * zz + w * x), 1 - 2 * (x * x + y * y)], axis=1)
-        assert float(np.abs(rows[:, sl["gravity"]] - grav).max()) <= 2e-6
-        self.prev = np.where(done[:, None], 0.0, a64)
-        self.air[done] = 0
-        self.cmd = obs[:, sl["command"]].astype(np.float64)
-        return rows
 
 
 def _check_body_velocity(rows, sl, rec, n):
@@ -116,7 +44,7 @@ def test_physics_untouched_quadruped(require_gpu):
     W, steps, H = 70, 60, 7
     kw = dict(action_mode="torque", home_base=(0, 0, 0.47, 1, 0, 0, 0), pid_gains=None, seed=11, joint_noise=0.05,
               max_episode_steps=H, action_scale=0.5, push_interval=7, push_steps=2, push_force=30.0, push_torque=5.0,
-              friction_range=(0.3, 1.2), **FREE, **LOCO)
+              friction_range=(0.3, 1.2), **FREE, **LOCO_EVERY_TERM)
     env = _make("quadruped", W, **kw)
     n, L = 8, 4
     assert (env.obs_dim, env.action_dim) == (25 + 3 * n + L, n) == (53, 8)
@@ -170,7 +98,7 @@ def test_physics_untouched_icub(require_gpu):
     import torch
     from mwstep.models import icub_pid_gains
     W, steps, n, L = 5, 60, 32, 2
-    kw = dict(max_episode_steps=0, action_scale=0.25, **FREE, **LOCO)
+    kw = dict(max_episode_steps=0, action_scale=0.25, **FREE, **LOCO_EVERY_TERM)
     env = _make("icub", W, **kw)
     assert (env.obs_dim, env.action_dim) == (25 + 3 * n + L, n) == (123, 32)
     gains = [[p, 0.0, d, -80.0, 80.0, 0.0, 0.0, -1.0] for p, d in icub_pid_gains(env.sim.joint_names)]
@@ -218,7 +146,7 @@ def test_air_time_touchdowns(require_gpu):
     import torch
     W, steps, n = 16, 40, 8
     kw = dict(action_mode="torque", home_base=(0, 0, 0.6, 1, 0, 0, 0), pid_gains=None, seed=13, joint_noise=0.05,
-              max_episode_steps=0, steps_per_run=10, **FREE, **LOCO)
+              max_episode_steps=0, steps_per_run=10, **FREE, **LOCO_EVERY_TERM)
     kw.update(command_ranges=((0.5, 1.0), (0.0, 0.0), (0.0, 0.0)), cmd_zero_prob=0.0, air_time_target=0.05)
     zero = np.zeros((W, n), np.float32)
     env = _make("quadruped", W, **kw)
@@ -256,10 +184,6 @@ def test_air_time_touchdowns(require_gpu):
     twin.close()
 
 
-def _philox(oracle, seed, world, episode, block):
-    return oracle.philox_raw([world, episode, block, 0], [seed & 0xFFFFFFFF, seed >> 32])
-
-
 def _command_ref(oracle, seed, world, episode, k, zero_prob, ranges=RANGES):
     """(is zero, the three words) of command k of the episode."""
     r = _philox(oracle, seed, world, episode, CMD_BLOCK | k)
@@ -287,7 +211,7 @@ def test_command_schedule(require_gpu, oracle):
         own = {tuple(ref(0, e, k)[1].tolist()) for e, k in read if not ref(0, e, k)[0]}
         return 0.15 < share < 0.35 and len(own) >= 5
     seed = next(s for s in range(1, 1000) if qualifies(s))
-    kw = dict(action_mode="torque", pid_gains=None, seed=seed, max_episode_steps=H, **FREE, **LOCO)
+    kw = dict(action_mode="torque", pid_gains=None, seed=seed, max_episode_steps=H, **FREE, **LOCO_EVERY_TERM)
     kw.update(cmd_interval=interval, cmd_zero_prob=zero_prob)
     env = _make("quadruped", W, **kw)
     part = _make("quadruped", 35, world_offset=35, **kw)
@@ -369,7 +293,7 @@ def test_graph_capture(require_gpu):
     of three kernel nodes."""
     import torch
     W, K = 70, 20
-    kw = dict(joint_noise=0.05, seed=4, max_episode_steps=6, **FREE, **LOCO)
+    kw = dict(joint_noise=0.05, seed=4, max_episode_steps=6, **FREE, **LOCO_EVERY_TERM)
     rng = np.random.default_rng(8)
     acts = rng.uniform(-0.8, 0.8, (K + 1, W, 8)).astype(np.float32)      # around the stand: action_scale 0.25
     plain = _make("quadruped", W, **kw)

@@ -16,59 +16,21 @@ Simulator given the delayed commands the test computes itself (the neutral
 command while t < d) ends every step with a bit-identical mw_get_state record;
 the delays equal the restated draw, word 2 of the episode block.  The reward's
 action terms and the last-action words follow the action just given
-(test_gpu_float_loco._RewardRef, at its bound)."""
+(float_env_harness._RewardRef, at its bound)."""
 
 import ctypes
-import math
 
 import numpy as np
 import pytest
 
-from test_gpu_float_env import STAND, _captured_step_graph, _make, _reset_twin, _twin
-from test_gpu_float_loco import FREE, LOCO, _RewardRef
+from float_env_harness import (FREE, LOCO_EVERY_TERM, STAND, _captured_step_graph, _check_rows, _delay_ref, _make,
+                               _reset_twin, _RewardRef, _twin)
 
 pytestmark = pytest.mark.gpu
 
-EPISODE_BLOCK = 0x40000000
 H = 7                                                 # steps per episode: resets interleave with the steps
 NOISE = dict(base_position=0.01, base_orientation=0.0, base_angular_velocity=0.05, joint_positions=0.02,
              joint_velocities=0.5, contacts=2.0, gravity=0.05, body_angular_velocity=0.1)
-
-
-def _key(seed):
-    return [seed & 0xFFFFFFFF, seed >> 32]
-
-
-def _noise_terms(oracle, seed, g, episode, t, amp):
-    """amp[k] u of one row in fp64, from the stated draw; words of amplitude zero draw nothing."""
-    out = np.zeros(len(amp))
-    for b in range((len(amp) + 3) // 4):
-        ks = [k for k in range(4 * b, min(4 * b + 4, len(amp))) if amp[k] != 0]
-        if ks:
-            x = oracle.philox_raw([g, episode, b, 1 + t], _key(seed))
-            for k in ks:
-                out[k] = float(amp[k]) * (-1.0 + float(int(x[k & 3]) >> 8) * 2.0 ** -23)
-    return out
-
-
-def _check_rows(oracle, seed, offset, amp, noisy, clean, worlds, episode, steps):
-    """Rows of `worlds`: noisy - clean is the stated draw; returns the worst error / bound."""
-    nz = amp != 0
-    worst = 0.0
-    for w in worlds:
-        c64 = clean[w].astype(np.float64)
-        ref = c64 + _noise_terms(oracle, seed, offset + int(w), int(episode[w]), int(steps[w]), amp)
-        bound = 2.0 ** -23 * (np.abs(c64) + amp.astype(np.float64))
-        err = np.abs(noisy[w].astype(np.float64) - ref)
-        assert (err[nz] <= bound[nz]).all(), f"world {w}: worst error / bound {(err[nz] / bound[nz]).max():.3f}"
-        worst = max(worst, float((err[nz] / bound[nz]).max()))
-        np.testing.assert_array_equal(noisy[w, ~nz].view(np.uint32), clean[w, ~nz].view(np.uint32))
-    return worst
-
-
-def _delay_ref(oracle, seed, g, episode, lo, hi):
-    r = oracle.philox_raw([g, episode, EPISODE_BLOCK, 0], _key(seed))
-    return lo + int(r[2]) % (hi - lo + 1)
 
 
 @pytest.mark.parametrize("kind, W, steps, spread, offset", [("quadruped", 70, 16, 0.8, 1000), ("icub", 3, 9, 0.4, 5)])
@@ -77,7 +39,7 @@ def test_noise_is_the_stated_draw(require_gpu, oracle, kind, W, steps, spread, o
     iCub: rows of 123 words > 64 lanes, so the word loop wraps."""
     import torch
     seed = 21
-    kw = dict(joint_noise=0.05, seed=seed, max_episode_steps=H, world_offset=offset, obs_noise=NOISE, **FREE, **LOCO)
+    kw = dict(joint_noise=0.05, seed=seed, max_episode_steps=H, world_offset=offset, obs_noise=NOISE, **FREE, **LOCO_EVERY_TERM)
     env = _make(kind, W, **kw)
     n, NO = env.action_dim, env.obs_dim
     assert NO == {"quadruped": 53, "icub": 123}[kind]
@@ -123,7 +85,7 @@ def test_noise_is_the_stated_draw(require_gpu, oracle, kind, W, steps, spread, o
 def test_clean_path_is_untouched(require_gpu):
     import torch
     W, steps = 70, 16
-    kw = dict(joint_noise=0.05, seed=22, max_episode_steps=H, **FREE, **LOCO)
+    kw = dict(joint_noise=0.05, seed=22, max_episode_steps=H, **FREE, **LOCO_EVERY_TERM)
     env = _make("quadruped", W, obs_noise=NOISE, **kw)
     plain = _make("quadruped", W, **kw)
     assert plain.obs_noise is None and plain.clean_obs is None and plain.action_delay is None
@@ -152,7 +114,7 @@ def test_shards_agree(require_gpu):
     import torch
     W, steps = 70, 16
     kw = dict(joint_noise=0.05, seed=23, max_episode_steps=H, obs_noise=NOISE, action_delay_range=(0, 3),
-              **FREE, **LOCO)
+              **FREE, **LOCO_EVERY_TERM)
     env = _make("quadruped", W, **kw)
     parts = [_make("quadruped", 35, world_offset=o, **kw) for o in (0, 35)]
     obs = env.reset().cpu().numpy()
@@ -190,7 +152,7 @@ def test_delay_torque_twin(require_gpu, oracle):
                    for e in range(steps // H + 1))
     seed = next(s for s in range(1, 1000) if qualifies(s))
     kw = dict(action_mode="torque", home_base=(0, 0, 0.47, 1, 0, 0, 0), pid_gains=None, seed=seed, joint_noise=0.05,
-              max_episode_steps=H, action_scale=0.5, action_delay_range=(lo, hi), **FREE, **LOCO)
+              max_episode_steps=H, action_scale=0.5, action_delay_range=(lo, hi), **FREE, **LOCO_EVERY_TERM)
     env = _make("quadruped", W, **kw)
     twin = _twin(env, "quadruped")
     obs = env.reset().cpu().numpy()
@@ -246,7 +208,7 @@ def test_delay_position_icub(require_gpu):
     from mwstep.models import icub_pid_gains
     W, steps, n = 3, 17, 32
     kw = dict(max_episode_steps=H, action_scale=0.25, joint_noise=0.02, seed=24, action_delay_range=(2, 2),
-              **FREE, **LOCO)
+              **FREE, **LOCO_EVERY_TERM)
     env = _make("icub", W, **kw)
     gains = [[p, 0.0, d, -80.0, 80.0, 0.0, 0.0, -1.0] for p, d in icub_pid_gains(env.sim.joint_names)]
     twin = _twin(env, "icub", gains)
@@ -310,7 +272,7 @@ def test_graph_capture(require_gpu):
     import torch
     W, K = 70, 5
     kw = dict(joint_noise=0.05, seed=26, max_episode_steps=3, obs_noise=NOISE, action_delay_range=(0, 3),
-              **FREE, **LOCO)
+              **FREE, **LOCO_EVERY_TERM)
     rng = np.random.default_rng(10)
     acts = rng.uniform(-0.8, 0.8, (K + 1, W, 8)).astype(np.float32)
     plain = _make("quadruped", W, **kw)

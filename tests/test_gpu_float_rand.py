@@ -13,22 +13,15 @@ is within 1.5 ulp at the magnitude |hi - lo|, hence the bound
 4 * 2^-23 * (hi - lo) between the two."""
 
 import ctypes
-import math
 
 import numpy as np
 import pytest
 
-from test_gpu_float_env import STAND, _make, _reset_twin, _twin, _unif32
+from float_env_harness import EPISODE_BLOCK, FREE, PUSH, STAND, _make, _philox, _reset_twin, _twin, _unif32
 
 pytestmark = pytest.mark.gpu
 
-PUSH = dict(push_interval=7, push_steps=2, push_force=30.0, push_torque=5.0)
-FREE = dict(z_min=-10.0, max_tilt=math.pi)           # no termination by height or tilt
-EPISODE_BLOCK, PUSH_BLOCK = 0x40000000, 0x80000000
-
-
-def _philox(oracle, seed, world, episode, block):
-    return oracle.philox_raw([world, episode, block, 0], [seed & 0xFFFFFFFF, seed >> 32])
+PUSH_BLOCK = 0x80000000
 
 
 def _phase(oracle, seed, world, episode, interval):

@@ -18,16 +18,14 @@ import math
 import numpy as np
 import pytest
 
+from float_env_harness import (ALL, FREE, LOCO_EVERY_TERM, STAND, _captured_step_graph, _dev, _forces32, _limits,
+                               _make, _params)
 from float_shape_ref import TERMS, ShapeHost
-from test_gpu_float_env import STAND, _captured_step_graph, _make
-from test_gpu_float_loco import FREE, LOCO
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
 W = 70                                                # two tiles, the second partial
-ALL = dict(torque=2e-5, power=1e-4, joint_acc=2.5e-7, orientation=1.0, base_height=10.0, joint_limits=5.0,
-           collision=1.0, stumble=0.5, contact_force=0.01, stand_still=0.2)
 # a soft limit the standing hips (0.6 of +-1.5) are already beyond, a foot force limit the stance exceeds
 SHAPE = dict(reward_terms=ALL, termination_links=("trunk",), termination_force=1.0, penalised_links=("trunk",),
              collision_force_min=0.1, base_height_target=0.4, soft_limit=0.3, stumble_ratio=0.2, max_contact_force=5.0)
@@ -40,38 +38,6 @@ def fs(tmp_path_factory):
     return ShapeHost(tmp_path_factory.mktemp("fs_gpu"))
 
 
-def _dev(env, a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(env.device)
-
-
-def _forces32(sim, w, links):
-    """The summed force vector of every link's contact points, float32, in the getters' (slot) order."""
-    c, b = sim.contacts(w), sim.contact_bodies(w)
-    out = np.zeros((len(links), 3), np.float32)
-    for j, link in enumerate(links):
-        f = np.zeros(3, np.float32)
-        for row in c[b == link]:
-            f = (f + row[6:9].astype(np.float32)).astype(np.float32)
-        out[j] = f
-    return out
-
-
-def _limits(fs, sim, soft):
-    from mwstep import native as N
-    n = sim.dofs
-    lower = np.float32([sim.joint_param(d, N.PARAM_POSITION_LIMIT_MIN) for d in range(n)])
-    upper = np.float32([sim.joint_param(d, N.PARAM_POSITION_LIMIT_MAX) for d in range(n)])
-    return fs.soft_limits(lower, upper, np.float32(soft))
-
-
-def _params(fs, env, kw):
-    g = lambda name, default: np.float32(kw.get(name, default))
-    return fs.params(kw.get("reward_terms", {}), g("base_height_target", env.home_base[2]),
-                     g("collision_force_min", 0.1), g("stumble_ratio", 5.0), g("max_contact_force", 100.0),
-                     g("termination_force", 1.0), np.float32(env.sim.steps_per_run * env.sim.step_size))
-
-
 def _kernel_order_sum(r0, terms):
     r = r0.astype(np.float32).copy()
     for k in range(10):
@@ -82,7 +48,7 @@ def _kernel_order_sum(r0, terms):
 def test_physics_and_the_old_reward_are_untouched(require_gpu):
     """Position mode, 30 steps of fixed random actions; every weight set, the trunk a termination and a
     penalised link that never touches the ground."""
-    kw = dict(seed=5, joint_noise=0.05, max_episode_steps=0, **FREE, **LOCO)
+    kw = dict(seed=5, joint_noise=0.05, max_episode_steps=0, **FREE, **LOCO_EVERY_TERM)
     on, off = _make("quadruped", W, **kw, **SHAPE), _make("quadruped", W, **kw)
     assert on.reward_term_names == TERMS and off.reward_terms is None
     np.testing.assert_array_equal(on.reset().cpu().numpy(), off.reset().cpu().numpy())
@@ -112,7 +78,7 @@ def test_terms_against_an_independent_recomputation(require_gpu, fs, case):
     """Each step the getters' q, qd, base pose and contact forces and env.torques go through the host harness;
     env.reward_terms must be those bits.  env.torques itself is checked against the action and the PID law."""
     position = case != "torque"
-    kw = dict(seed=6, joint_noise=0.05, max_episode_steps=0, action_scale=0.0, **FREE, **LOCO)
+    kw = dict(seed=6, joint_noise=0.05, max_episode_steps=0, action_scale=0.0, **FREE, **LOCO_EVERY_TERM)
     if position:
         kw.update(pid_gains=P_ONLY)
     else:
@@ -164,7 +130,7 @@ def test_terms_against_an_independent_recomputation(require_gpu, fs, case):
         q, qd, pose = sim.get("q").astype(np.float32), sim.get("qd").astype(np.float32), sim.base_pose()
         for w in range(W):
             cf, pf = _forces32(sim, w, env.contact_links), _forces32(sim, w, env.penalised_links)
-            standing = fs.standing(cmd[w, 0], cmd[w, 1], LOCO["cmd_min"])
+            standing = fs.standing(cmd[w, 0], cmd[w, 1], LOCO_EVERY_TERM["cmd_min"])
             _, expect = fs.world(par, tau[w], q[w], qd[w], qd_prev[w], lo, hi, env.home_q, cf, pf, pose[w], standing)
             np.testing.assert_array_equal(terms[w], expect, err_msg=f"step {k}, world {w}")
         seen |= (terms < 0).any(axis=0)
@@ -349,7 +315,7 @@ def test_icub(require_gpu, fs):
 def test_graph_capture_and_defaults(require_gpu):
     import torch
     K = 20
-    kw = dict(joint_noise=0.05, seed=4, max_episode_steps=6, **FREE, **LOCO, **SHAPE)
+    kw = dict(joint_noise=0.05, seed=4, max_episode_steps=6, **FREE, **LOCO_EVERY_TERM, **SHAPE)
     rng = np.random.default_rng(8)
     acts = (np.float32(STAND) + rng.uniform(-0.2, 0.2, (K + 1, W, 8))).astype(np.float32)
     outputs = ("obs", "reward", "done", "reward_terms", "torques", "episode_return", "episode_length", "episode_terms")

@@ -14,7 +14,7 @@ on the MI355X pool).  tests/sanitize/Makefile builds four drivers with
     (tests/host_dyn/harness.cpp): chain / tree substeps with constraint rows
     and the floating-tree step with contacts;
   * lifecycle_san -- the library's host layer (csrc/sim.cpp, world_params.cpp,
-    vecenv.cpp, scene.cpp) over a stand-in for the HIP runtime (hip_standin.cpp): every
+    vecenv.cpp, floatenv.cpp, scene.cpp) over a stand-in for the HIP runtime (hip_standin.cpp): every
     handle's life from create to destroy, cleanly and with each creating call
     (buffer, stream, event) failing in turn.
 
