@@ -38,6 +38,11 @@
 // ft_shape_stats); the [W, 10] rows leave through two small LDS tiles as
 // contiguous spans.  In torque mode the action launch keeps the command it
 // stored in an array of the env, through a nullable argument.
+// Initial-state randomisation and the reset-state bank (mw_floatenv_init_state)
+// are the third such branch (T.init.on), in the post launch's reset block
+// alone: a done world starts from a row of the caller's bank or the home row
+// plus drawn offsets (init_reset) where the plain reset writes constants, and
+// the first words of the reset rows leave once more as T.init.state_out.
 //
 // Both kernels are transposes between the row-major [W, k] tensors of the
 // agent and the [k][W] SoA arrays of the simulator.  A block of 256 threads
@@ -349,6 +354,130 @@ __device__ __forceinline__ void shape_terms(const FloatShapeF& H, const float* p
     ft_shape_terms(H, x, diverged, term);
 }
 
+// The reset of one done world with the initial-state randomisation on
+// (mw_floatenv_init_state, T.init.on; lane = world, called by every wave of the
+// lane): it takes the place of the plain reset's joint loop and base block and
+// leaves the same words -- the pending joint and base resets with their flags,
+// the divergence flag re-armed, the reset row in the tile -- from a base row
+// plus draws (float_task.hpp).  A wave that has work draws the row choice
+// itself (one Philox call, only with a bank) rather than wait for another's
+// through LDS: the reset block has no barrier.  The joints go in blocks of four
+// round the waves as in the plain reset, the same Philox blocks for the
+// position noise and one more call per block for the velocity draws; a wave's
+// words of the base row are the block's four q and four qd, the gather of one
+// row per done lane split over the waves.  The home row is read the same way,
+// from a copy in device memory (T.init.home): a choice between a word of the
+// bank and a word of T would make the compiler select between their addresses,
+// and a by-value argument whose address is taken is copied to scratch, in
+// every instance and with the feature off too.  The base -- the row's 13 words, the
+// four groups' draws, the composed orientation, in the locomotion task (loco_nb
+// >= 0: the first word of the appended block) the projected gravity and the
+// body-frame velocities of the drawn state -- is wave kInitBaseWave's, a wave
+// the other reset draws load least.  With shaping on the drawn qd is the kept
+// qd of the first step's joint_acc term: written here by the wave that drew
+// it, behind the barriers that follow the gather's store of the same word.  A
+// non-finite q of a bank row stays non-finite (the clip alone would turn a NaN
+// into the lower limit): the run flags the world diverged.
+constexpr int kInitBaseWave = 2;
+__device__ __forceinline__ void init_reset(const ChainF* __restrict__ P, const FloatTaskF& T, const SimDev& S,
+                                           const FreeDev& D, int n, size_t Ws, int w, int wave, uint32_t episode,
+                                           bool shaped, int loco_nb, float* row) {
+    const FloatInitF& I = T.init;
+    const uint32_t g = T.world_offset + static_cast<uint32_t>(w);
+    const int NS = 13 + 2 * n, nblocks = (n + 3) / 4;
+    const bool base_wave = wave == kInitBaseWave;
+    if (!base_wave && wave >= nblocks) return;
+    int32_t k_row = -1;
+    if (I.n_states > 0) {
+        uint32_t r[4];
+        philox(T.seed_lo, T.seed_hi, g, episode, r, kFtInitRowBlock);
+        k_row = ft_init_row(r[0], r[1], I.n_states, I.state_prob);
+    }
+    // one pointer for either kind of start: the home row is a row in device memory too (the env's own)
+    const float* __restrict__ base_row = k_row >= 0 ? I.states + static_cast<size_t>(k_row) * NS : I.home;
+    float* __restrict__ draws = I.draws_out ? I.draws_out + static_cast<size_t>(w) * (kInitBaseDraws + n) : nullptr;
+    const bool jv = I.joint_vel > 0.f;
+    for (int b = wave; b < nblocks; b += kEnvWaves) {
+        uint32_t r[4], rv[4] = {0u, 0u, 0u, 0u};
+        philox(T.seed_lo, T.seed_hi, g, episode, r, static_cast<uint32_t>(b));
+        if (jv) philox(T.seed_lo, T.seed_hi, g, episode, rv, ft_init_qd_block(4 * b));
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int d = 4 * b + k;
+            if (d < n) {
+                const float q0 = base_row[13 + d], qd0 = base_row[13 + n + d];
+                const float x = q0 + unif(r[k], -T.joint_noise, T.joint_noise);
+                const float clipped = fminf(fmaxf(x, P->b[d].lower), P->b[d].upper);
+                const float q = nonfinite_bits(x) ? x : clipped;  // by the bits: the build assumes finite math
+                const float dv = jv ? ft_unif(rv[k], -I.joint_vel, I.joint_vel) : 0.f;
+                const float qd = jv ? ft_init_sum(qd0, dv) : qd0;
+                const size_t i = d * Ws + w;
+                S.rq[i] = q;
+                S.rqd[i] = qd;
+                S.rflag[i] = 1u | 2u | 4u;  // position, velocity, PID reset
+                row[13 + d] = q;
+                row[13 + n + d] = qd;
+                if (shaped) T.shape.qd_prev[i] = qd;
+                if (draws) draws[kInitBaseDraws + d] = dv;
+            }
+        }
+    }
+    if (!base_wave) return;
+    float rowb[13];
+#pragma unroll
+    for (int k = 0; k < 13; ++k) rowb[k] = base_row[k];
+    float off[4][3] = {{0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}, {0.f, 0.f, 0.f}};
+    uint32_t r[4];
+    if (I.groups & kInitPos) {
+        philox(T.seed_lo, T.seed_hi, g, episode, r, kFtInitPosBlock);
+        ft_init_offsets(r, I.pos_lo, I.pos_hi, off[0]);
+    }
+    if (I.groups & kInitRpy) {
+        philox(T.seed_lo, T.seed_hi, g, episode, r, kFtInitRpyBlock);
+        ft_init_offsets(r, I.rpy_lo, I.rpy_hi, off[1]);
+    }
+    if (I.groups & kInitLin) {
+        philox(T.seed_lo, T.seed_hi, g, episode, r, kFtInitLinBlock);
+        ft_init_offsets(r, I.lin_lo, I.lin_hi, off[2]);
+    }
+    if (I.groups & kInitAng) {
+        philox(T.seed_lo, T.seed_hi, g, episode, r, kFtInitAngBlock);
+        ft_init_offsets(r, I.ang_lo, I.ang_hi, off[3]);
+    }
+    float base[13], qn[4];
+    ft_init_base(I, rowb, off[0], off[1], off[2], off[3], base, qn);
+#pragma unroll
+    for (int k = 0; k < 7; ++k) {
+        D.rpose[k * Ws + w] = base[k];
+        row[k] = base[k];
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        D.rvel[k * Ws + w] = base[7 + k];
+        row[7 + k] = base[7 + k];
+    }
+    D.rflag[w] = 1u | 2u;
+    S.div[w] = 0;  // a reset re-arms the divergence flag (mw_reset_* do)
+    if (loco_nb >= 0) {
+        const float lin[3] = {base[7], base[8], base[9]}, ang[3] = {base[10], base[11], base[12]};
+        float gr[3], v[3], om[3];
+        ft_projected_gravity(qn[0], qn[1], qn[2], qn[3], gr);
+        ft_init_body_frame(qn, lin, v);
+        ft_init_body_frame(qn, ang, om);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            row[loco_nb + k] = gr[k];
+            row[loco_nb + 3 + k] = v[k];
+            row[loco_nb + 6 + k] = om[k];
+        }
+    }
+    if (draws) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) draws[k] = off[k / 3][k % 3];
+        draws[12] = static_cast<float>(k_row);
+    }
+}
+
 // Per world: gather the observation, reward, done, counters; where done, the
 // terminal observation, the reset sample written as pending resets (exactly
 // the bits and values mw_reset_joint_positions + mw_reset_joint_velocities +
@@ -433,6 +562,7 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
     const int w = w0 + lane;
     const bool live = lane < rows;
     const bool noisy = T.noise.amp != nullptr;  // block-uniform
+    const bool starts = __builtin_expect(T.init.on != 0u, 0);  // block-uniform: the reset state is drawn (init_reset)
     float* row = tile + lane * pitch;
     const size_t Ws = static_cast<size_t>(W);
     if (!reset_all) {
@@ -627,25 +757,30 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
     // pid_task_reset; the base at home_base, everything at rest
     if (live && s_done[lane]) {
         const uint32_t episode = s_episode[lane];
-        for (int b = wave; b < (n + 3) / 4; b += kEnvWaves) {
-            uint32_t r[4];
-            philox(T.seed_lo, T.seed_hi, T.world_offset + static_cast<uint32_t>(w), episode, r, static_cast<uint32_t>(b));
+        if (starts) {
+            init_reset(P, T, S, D, n, Ws, w, wave, episode, shaped, LOCO ? NB : -1, row);
+        } else {
+            for (int b = wave; b < (n + 3) / 4; b += kEnvWaves) {
+                uint32_t r[4];
+                philox(T.seed_lo, T.seed_hi, T.world_offset + static_cast<uint32_t>(w), episode, r,
+                       static_cast<uint32_t>(b));
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int d = 4 * b + k;
-                if (d < n) {
-                    const float x = T.home_q[d] + unif(r[k], -T.joint_noise, T.joint_noise);
-                    const float q = fminf(fmaxf(x, P->b[d].lower), P->b[d].upper);
-                    const size_t i = d * Ws + w;
-                    S.rq[i] = q;
-                    S.rqd[i] = 0.f;
-                    S.rflag[i] = 1u | 2u | 4u;  // position, velocity, PID reset
-                    row[13 + d] = q;
-                    row[13 + n + d] = 0.f;
+                for (int k = 0; k < 4; ++k) {
+                    const int d = 4 * b + k;
+                    if (d < n) {
+                        const float x = T.home_q[d] + unif(r[k], -T.joint_noise, T.joint_noise);
+                        const float q = fminf(fmaxf(x, P->b[d].lower), P->b[d].upper);
+                        const size_t i = d * Ws + w;
+                        S.rq[i] = q;
+                        S.rqd[i] = 0.f;
+                        S.rflag[i] = 1u | 2u | 4u;  // position, velocity, PID reset
+                        row[13 + d] = q;
+                        row[13 + n + d] = 0.f;
+                    }
                 }
             }
         }
-        if (wave == 0) {
+        if (!starts && wave == 0) {
 #pragma unroll
             for (int k = 0; k < 7; ++k) {
                 D.rpose[k * Ws + w] = T.home_base[k];
@@ -769,7 +904,7 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
             row[13 + 2 * n + j] = 0.f;
             if constexpr (LOCO) T.loco.air_steps[j * Ws + w] = 0u;
         }
-        if (shaped) {
+        if (shaped && !starts) {
             // joint_acc of an episode's first step is taken from rest (the wave that wrote the word)
             for (int d = wave; d < n; d += kEnvWaves) T.shape.qd_prev[d * Ws + w] = 0.f;
         }
@@ -794,6 +929,14 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
         for (int k = 0; k < 3; ++k) T.loco.command_out[static_cast<size_t>(w) * 3 + k] = row[NB + 9 + k];
     }
     __syncthreads();
+    if (starts && T.init.state_out) {
+        // the state the new episodes start from: the first 13 + 2 n words of their clean reset rows
+        const int NS = 13 + 2 * n;
+        float* __restrict__ state_out = T.init.state_out;
+        for (int r = wave; r < rows; r += kEnvWaves)
+            if (s_done[r])
+                for (int k = lane; k < NS; k += 64) state_out[static_cast<size_t>(w0 + r) * NS + k] = tile[r * pitch + k];
+    }
     // (the noise of the episode and step count the row belongs to: the updated counters)
     if (noisy) {
         ft_write_noisy(T, tile, pitch, rows, w0, obs, T.noise.clean_obs, nullptr, s_episode, 0u, s_steps);

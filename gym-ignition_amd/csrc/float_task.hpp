@@ -17,7 +17,10 @@
 // draw and the ring's slots), built by tests/host_float_noise/harness.cpp, and
 // that of the shaping rewards, the contact termination and the episode
 // statistics (mw_floatenv_shaping: the ten terms, the slot predicate, the
-// accumulator step), built by tests/host_float_shape/harness.cpp.
+// accumulator step), built by tests/host_float_shape/harness.cpp, and that of
+// the initial-state randomisation (mw_floatenv_init_state: the row choice, the
+// offsets, the composed orientation, the velocity sums), built by
+// tests/host_float_init/harness.cpp.
 #pragma once
 
 #ifdef MW_HOST_TEST
@@ -177,6 +180,36 @@ struct FloatShapeF {
     float* ep_terms;               // [W, 10]
 };
 
+// Initial-state randomisation and the reset-state bank of the floating-base
+// env (mw_floatenv_init_state), off when `on` is zero.  An episode starts from
+// a base row of 13 + 2 n words in the layout of a row of obs (position,
+// quaternion wxyz, world linear and angular velocity, q, qd) -- the home row,
+// or a row of the bank -- plus the draws below, each group off when its bit of
+// `groups` is clear.
+enum InitGroup : uint32_t { kInitPos = 1u, kInitRpy = 2u, kInitLin = 4u, kInitAng = 8u };
+constexpr int kInitBaseDraws = 13;  // dpos, roll pitch yaw, dlin, dang, the bank row: then n joint-velocity draws
+struct FloatInitF {
+    uint32_t on;
+    uint32_t groups;               // InitGroup bits
+    float pos_lo[3], pos_hi[3];    // added to the base position (m, world frame)
+    float rpy_lo[3], rpy_hi[3];    // roll, pitch, yaw (rad): qz(yaw) qy(pitch) qx(roll) q_row
+    float lin_lo[3], lin_hi[3];    // added to the world linear velocity (m/s)
+    float ang_lo[3], ang_hi[3];    // added to the world angular velocity (rad/s)
+    float joint_vel;               // qd_d = row_qd_d + U(-joint_vel, joint_vel); on when > 0
+    float state_prob;              // a bank row where U(0, 1) of r[1] < state_prob, else the home row
+    int32_t n_states;              // rows of the bank, 0 = none
+    const float* states;           // [n_states, 13 + 2 n] the bank (caller's, read at every reset)
+    const float* home;             // [13 + 2 n] the home row: home_base, zeros, home_q, zeros (the env's own)
+    float* state_out;              // [W, 13 + 2 n] the state the current episode started from (caller's, may be null)
+    float* draws_out;              // [W, 13 + n] the episode's draws (caller's, may be null)
+};
+constexpr uint32_t kFtInitRowBlock = 0x40000300u;  // r[0]: bank row, r[1]: bank or home row
+constexpr uint32_t kFtInitPosBlock = 0x40000301u;  // r[0..2]: position offsets
+constexpr uint32_t kFtInitRpyBlock = 0x40000302u;  // r[0..2]: roll, pitch, yaw
+constexpr uint32_t kFtInitLinBlock = 0x40000303u;  // r[0..2]: linear velocity offsets
+constexpr uint32_t kFtInitAngBlock = 0x40000304u;  // r[0..2]: angular velocity offsets
+constexpr uint32_t kFtInitQdBlock = 0x40000340u;   // | d / 4, word d % 4: velocity draw of joint d < 48
+
 // Task description of the floating-base env (kernel argument, by value).
 struct FloatTaskF {
     int32_t action_mode;     // 0 torque (SimDev::cmd), 1 position (SimDev::ptgt)
@@ -197,6 +230,7 @@ struct FloatTaskF {
     FloatJointF joints;
     FloatNoiseF noise;
     FloatShapeF shape;
+    FloatInitF init;
 };
 
 namespace dev {
@@ -587,6 +621,108 @@ __device__ __forceinline__ bool ft_shape_stats(float reward, const float (&term)
         acc_terms[k] = 0.f;
     }
     return true;
+}
+
+// ---- initial-state randomisation and the reset-state bank (FloatInitF) ----
+
+// The bank row an episode starts from, from words 0 and 1 of its row block:
+// r_a % K where U(0, 1) of r_b (an exact float32) is below state_prob, else -1,
+// the home row.  state_prob 1 always takes the bank (U < 1), 0 never.
+__device__ __forceinline__ int32_t ft_init_row(uint32_t r_a, uint32_t r_b, int32_t n_states, float state_prob) {
+    if (n_states <= 0 || !(ft_unif(r_b, 0.f, 1.f) < state_prob)) return -1;
+    return static_cast<int32_t>(r_a % static_cast<uint32_t>(n_states));
+}
+// Philox block of joint d's velocity draw; its word is d % 4
+__device__ __forceinline__ uint32_t ft_init_qd_block(int d) { return kFtInitQdBlock | static_cast<uint32_t>(d >> 2); }
+
+// The three offsets of a group from words 0..2 of its block
+__device__ __forceinline__ void ft_init_offsets(const uint32_t (&r)[4], const float (&lo)[3], const float (&hi)[3],
+                                                float (&d)[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) d[k] = ft_unif(r[k], lo[k], hi[k]);
+}
+
+// A row's word plus its draw, one rounding (a position, a velocity)
+__device__ __forceinline__ float ft_init_sum(float word, float draw) {
+    MW_FT_NO_CONTRACT
+    return word + draw;
+}
+
+// q / |q|: the square sum ((w^2 + x^2) + y^2) + z^2 in fused steps, one
+// square root, one quotient, four products
+__device__ __forceinline__ void ft_init_normalise(float (&q)[4]) {
+    MW_FT_NO_CONTRACT
+    const float ww = q[0] * q[0];
+    const float wx = fmaf(q[1], q[1], ww);
+    const float wy = fmaf(q[2], q[2], wx);
+    const float n2 = fmaf(q[3], q[3], wy);
+    const float inv = 1.f / sqrtf(n2);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = q[k] * inv;
+}
+
+// The reset orientation qz(yaw) qy(pitch) qx(roll) q_row, normalised: three
+// world-frame rotations after the row's own, each a Hamilton product with a
+// quaternion of two nonzero words (one product and one fused multiply-add per
+// component), sinf / cosf of the half angles.  An angle of zero leaves its
+// factor exact (c = 1, s = 0).
+__device__ __forceinline__ void ft_init_orientation(const float (&rpy)[3], const float (&q_row)[4], float (&q)[4]) {
+    MW_FT_NO_CONTRACT
+    float h, c, s, a[4], b[4];
+    h = 0.5f * rpy[0]; c = cosf(h); s = sinf(h);
+    {
+        const float cw = c * q_row[0], cx = c * q_row[1], cy = c * q_row[2], cz = c * q_row[3];
+        a[0] = fmaf(-s, q_row[1], cw); a[1] = fmaf(s, q_row[0], cx);
+        a[2] = fmaf(-s, q_row[3], cy); a[3] = fmaf(s, q_row[2], cz);
+    }
+    h = 0.5f * rpy[1]; c = cosf(h); s = sinf(h);
+    {
+        const float cw = c * a[0], cx = c * a[1], cy = c * a[2], cz = c * a[3];
+        b[0] = fmaf(-s, a[2], cw); b[1] = fmaf(s, a[3], cx);
+        b[2] = fmaf(s, a[0], cy); b[3] = fmaf(-s, a[1], cz);
+    }
+    h = 0.5f * rpy[2]; c = cosf(h); s = sinf(h);
+    {
+        const float cw = c * b[0], cx = c * b[1], cy = c * b[2], cz = c * b[3];
+        q[0] = fmaf(-s, b[3], cw); q[1] = fmaf(-s, b[2], cx);
+        q[2] = fmaf(s, b[1], cy); q[3] = fmaf(s, b[0], cz);
+    }
+    ft_init_normalise(q);
+}
+
+// R^T v with R of the unit quaternion q: a world vector in the body frame (the
+// body-frame velocities of the locomotion rows)
+__device__ __forceinline__ void ft_init_body_frame(const float (&q)[4], const float (&v)[3], float (&out)[3]) {
+    float R[9];
+    ft_rotation(q[0], q[1], q[2], q[3], R);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = R[k] * v[0] + R[3 + k] * v[1] + R[6 + k] * v[2];
+}
+
+// The base words of a reset from its base row (13 words) and the four groups'
+// draws: base[0..12] the words of the reset row (and of D.rpose / D.rvel), qn
+// the unit quaternion of the start (base[3..6] itself with the orientation
+// group on, else the row's normalised: the row's own words are then written
+// as they are and the run normalises what it takes).
+__device__ __forceinline__ void ft_init_base(const FloatInitF& I, const float (&row)[13], const float (&dpos)[3],
+                                             const float (&rpy)[3], const float (&dlin)[3], const float (&dang)[3],
+                                             float (&base)[13], float (&qn)[4]) {
+    const float q_row[4] = {row[3], row[4], row[5], row[6]};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        base[k] = (I.groups & kInitPos) ? ft_init_sum(row[k], dpos[k]) : row[k];
+        base[7 + k] = (I.groups & kInitLin) ? ft_init_sum(row[7 + k], dlin[k]) : row[7 + k];
+        base[10 + k] = (I.groups & kInitAng) ? ft_init_sum(row[10 + k], dang[k]) : row[10 + k];
+    }
+    if (I.groups & kInitRpy) {
+        ft_init_orientation(rpy, q_row, qn);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) base[3 + k] = qn[k];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) base[3 + k] = qn[k] = q_row[k];
+        ft_init_normalise(qn);
+    }
 }
 
 #undef MW_FT_NO_CONTRACT

@@ -13,6 +13,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <vector>
 
 #include "errors.hpp"
 #include "vecenv_state.hpp"
@@ -488,6 +489,78 @@ int mw_floatenv_shaping(mw_vecenv* e, const mw_float_shape_config* cfg, float* t
     H.ep_return = ep_return;
     H.ep_length = ep_length;
     H.ep_terms = ep_terms;
+    return MW_OK;
+}
+
+// Initial-state randomisation and the reset-state bank of a floating-base env:
+// one more block-uniform runtime branch of the post launch's reset block
+// (float_env_kernel.hip, T.init.on), which draws where an episode starts -- a
+// row of the caller's bank or the home row, plus offsets -- into the pending
+// resets.  The bank and the two outputs are the caller's; the env's own is a
+// copy of the home row in device memory, which the kernel reads as it reads a
+// bank row.
+int mw_floatenv_init_state(mw_vecenv* e, const mw_float_init_config* cfg, const float* states_dev, float* state_dev,
+                           float* draws_dev) {
+    if (int rc = check_configurable(e, cfg, "mw_floatenv_init_state")) return rc;
+    struct Range {
+        const float (&lo)[3];
+        const float (&hi)[3];
+        uint32_t bit;
+        const char* name;
+    };
+    const Range ranges[] = {{cfg->pos_lo, cfg->pos_hi, mw::kInitPos, "pos"},
+                            {cfg->rpy_lo, cfg->rpy_hi, mw::kInitRpy, "rpy"},
+                            {cfg->lin_vel_lo, cfg->lin_vel_hi, mw::kInitLin, "lin_vel"},
+                            {cfg->ang_vel_lo, cfg->ang_vel_hi, mw::kInitAng, "ang_vel"}};
+    uint32_t groups = 0u;
+    for (const Range& r : ranges)
+        for (int k = 0; k < 3; ++k) {
+            if (!std::isfinite(r.lo[k]) || !std::isfinite(r.hi[k]))
+                return fail(MW_EINVAL, "every field of mw_float_init_config must be finite");
+            if (r.lo[k] > r.hi[k])
+                return fail(MW_EINVAL, std::string("the ") + r.name + " range needs " + r.name + "_lo <= " + r.name + "_hi");
+            if (r.lo[k] != 0.f || r.hi[k] != 0.f) groups |= r.bit;
+        }
+    if (!std::isfinite(cfg->joint_vel) || !std::isfinite(cfg->state_prob))
+        return fail(MW_EINVAL, "every field of mw_float_init_config must be finite");
+    if (cfg->joint_vel < 0.f) return fail(MW_EINVAL, "joint_vel must be >= 0");
+    if (cfg->state_prob < 0.f || cfg->state_prob > 1.f) return fail(MW_EINVAL, "state_prob must be in [0, 1]");
+    if (cfg->n_states < 0) return fail(MW_EINVAL, "n_states must be >= 0");
+    if (cfg->n_states > 0 && !states_dev) return fail(MW_EINVAL, "n_states > 0 needs the bank: states_dev is null");
+    if (cfg->n_states == 0 && states_dev) return fail(MW_EINVAL, "a bank (states_dev) needs n_states > 0");
+    mw_sim* s = e->sim;
+    mw::FloatEnv& F = *e->fenv;
+    mw::FloatInitF& I = F.ftask.init;
+    if (!groups && cfg->joint_vel == 0.f && cfg->n_states == 0 && !state_dev && !draws_dev) {
+        I = mw::FloatInitF{};  // everything off: the env as it was made
+        F.d_init_home.reset();
+        return MW_OK;
+    }
+    const size_t n = static_cast<size_t>(s->n), words = 13 + 2 * n;
+    std::vector<float> home_row(words, 0.f);
+    for (int k = 0; k < 7; ++k) home_row[k] = F.ftask.home_base[k];
+    for (size_t d = 0; d < n; ++d) home_row[13 + d] = F.ftask.home_q[d];
+    MW_HIP(hipSetDevice(s->cfg.device));
+    mw::dev_ptr<float[]> home;
+    MW_HIP(mw::dev_alloc(home, words * sizeof(float)));
+    MW_HIP(hipMemcpy(home.get(), home_row.data(), words * sizeof(float), hipMemcpyHostToDevice));  // complete on return
+    F.d_init_home = std::move(home);
+    I = mw::FloatInitF{};
+    I.on = 1u;
+    I.home = F.d_init_home.get();
+    I.groups = groups;
+    for (int k = 0; k < 3; ++k) {
+        I.pos_lo[k] = cfg->pos_lo[k]; I.pos_hi[k] = cfg->pos_hi[k];
+        I.rpy_lo[k] = cfg->rpy_lo[k]; I.rpy_hi[k] = cfg->rpy_hi[k];
+        I.lin_lo[k] = cfg->lin_vel_lo[k]; I.lin_hi[k] = cfg->lin_vel_hi[k];
+        I.ang_lo[k] = cfg->ang_vel_lo[k]; I.ang_hi[k] = cfg->ang_vel_hi[k];
+    }
+    I.joint_vel = cfg->joint_vel;
+    I.state_prob = cfg->state_prob;
+    I.n_states = cfg->n_states;
+    I.states = states_dev;
+    I.state_out = state_dev;
+    I.draws_out = draws_dev;
     return MW_OK;
 }
 

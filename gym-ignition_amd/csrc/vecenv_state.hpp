@@ -37,6 +37,8 @@ struct FloatEnv {
     dev_ptr<float[]> d_shape_cmd;
     dev_ptr<float[]> d_shape_sums;
     dev_ptr<int32_t[]> d_shape_length;
+    // initial-state randomisation (mw_floatenv_init_state): the home row [13 + 2 n]
+    dev_ptr<float[]> d_init_home;
 };
 
 }  // namespace mw

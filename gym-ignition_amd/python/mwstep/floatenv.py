@@ -50,6 +50,13 @@ collisions of non-foot links, stumbling, excessive foot forces, standing still
 -- as ten signed reward columns (``env.reward_terms``), a termination on
 contact of chosen links, and per-episode statistics of the finished episodes
 (``env.episode_return``, ``env.episode_length``, ``env.episode_terms``).
+
+``init_states=``, ``init_pos_range=``, ``init_rpy_range=``,
+``init_lin_vel_range=``, ``init_ang_vel_range=`` and ``init_joint_vel=``
+(``mw_floatenv_init_state``) vary where an episode starts, drawn by the launch
+that issues the reset: from a row of a bank of recorded states or the home
+state, plus offsets on the base pose, the base velocity and the joint
+velocities (``env.init_state``, ``env.init_draws``).
 """
 
 from __future__ import annotations
@@ -138,7 +145,13 @@ class FloatVecEnv:
                  reward_terms: Optional[Mapping] = None, termination_links: Optional[Sequence] = None,
                  termination_force: float = 1.0, penalised_links: Sequence = (), collision_force_min: float = 0.1,
                  base_height_target: Optional[float] = None, soft_limit: float = 0.9, stumble_ratio: float = 5.0,
-                 max_contact_force: float = 100.0):
+                 max_contact_force: float = 100.0,
+                 init_states=None, init_state_prob: float = 1.0,
+                 init_pos_range: Optional[Sequence[Sequence[float]]] = None,
+                 init_rpy_range: Optional[Sequence[Sequence[float]]] = None,
+                 init_lin_vel_range: Optional[Sequence[Sequence[float]]] = None,
+                 init_ang_vel_range: Optional[Sequence[Sequence[float]]] = None,
+                 init_joint_vel: Optional[float] = None):
         """``model``: a shipped model's name or a URDF / SDF file.  ``home_q``
         (one value per dof) and ``home_base`` (x y z qw qx qy qz) are the reset
         state; ``pid_gains`` per dof ``(p, i, d)`` or the eight values of
@@ -257,7 +270,49 @@ class FloatVecEnv:
         return, length and term sums of the last finished episode of each
         world, valid where that world has been ``done`` (``reset()`` starts the
         running sums over and leaves these three alone).  All are mirrored in ``info``
-        under the same names and are ``None`` with the feature off."""
+        under the same names and are ``None`` with the feature off.
+
+        Initial-state randomisation and the reset-state bank
+        (``mw_floatenv_init_state``), on when ``init_states`` or any of the
+        ``init_*`` ranges is given; every reset then draws where the episode
+        starts, inside the same launches, as a pure function of (seed, global
+        world, episode).  An episode starts from a base row of ``13 + 2 n``
+        words in the layout of ``obs[:, :13 + 2 n]`` -- base position,
+        quaternion wxyz, world linear and angular velocity, ``q``, ``qd`` --
+        so a recorded observation row is a valid row.  Without a bank it is the
+        home row (``home_base``, ``home_q``, at rest).  ``init_states``: a
+        contiguous float32 tensor ``[K, 13 + 2 n]`` on the env's device; an
+        episode starts from one of its rows with probability
+        ``init_state_prob`` (default 1), else from the home row.  The env keeps
+        the tensor and reads it at every reset: rows overwritten between two
+        steps (on the env's stream) are what the next resets see.  What a row
+        holds is the caller's business: a zero quaternion or a non-finite word
+        gives a non-finite state, which ends at the next step like any diverged
+        world and is reset.  On top of the row, each off unless given:
+        ``init_pos_range``, three ``(lo, hi)`` pairs (m) added to the base
+        position in the world frame; ``init_rpy_range``, three ``(lo, hi)``
+        pairs (rad) for roll, pitch and yaw, world-frame rotations applied
+        after the row's own orientation (``qz(yaw) qy(pitch) qx(roll) q_row``,
+        normalised; without it the row's quaternion is taken as it is);
+        ``init_lin_vel_range`` and ``init_ang_vel_range``, three ``(lo, hi)``
+        pairs each, added to the row's world linear (m/s) and angular (rad/s)
+        velocity; ``init_joint_vel`` ``v >= 0``: every joint velocity gains
+        U(-v, v).  Joint positions are the row's plus ``joint_noise`` as
+        before, clipped into the position limits.  The reset observation is
+        that of the drawn state (in the locomotion task its gravity and
+        body-velocity words too), and the ``joint_acc`` term of an episode's
+        first step is taken from the drawn joint velocities.  Nothing checks a
+        drawn state against ``z_min``, ``max_tilt`` or the ground: a start
+        beyond the first two simply ends at the next step, and a start below
+        the ground is yours to avoid through the ranges.  ``env.init_state``
+        ``[n_worlds, 13 + 2 n]`` (also ``info["init_state"]``) holds the state
+        the current episode started from -- the first words of the clean reset
+        row -- and ``env.init_draws`` ``[n_worlds, 13 + n]``
+        (``info["init_draws"]``) the draws themselves: position offsets (3),
+        roll pitch yaw (3), linear (3) and angular (3) velocity offsets, the
+        bank row as a float (-1 for the home row) and the ``n`` joint-velocity
+        draws; both change where, and only where, an episode ended, and are
+        ``None`` with the feature off."""
         torch = _torch()
         if action_mode not in ACTION_MODES:
             raise ValueError(f"unknown action_mode {action_mode!r}; known: {sorted(ACTION_MODES)}")
@@ -352,6 +407,8 @@ class FloatVecEnv:
         self._setup_noise(obs_noise, action_delay_range)
         self._setup_shaping(model_file, reward_terms, termination_links, termination_force, penalised_links,
                             collision_force_min, base_height_target, soft_limit, stumble_ratio, max_contact_force)
+        self._setup_init_state(init_states, init_state_prob, init_pos_range, init_rpy_range, init_lin_vel_range,
+                               init_ang_vel_range, init_joint_vel)
 
     def _zeros(self, *shape, dtype=None):
         torch = _torch()
@@ -488,6 +545,36 @@ class FloatVecEnv:
         self._info.update(reward_terms=self.reward_terms, torques=self.torques,
                           episode_return=self.episode_return, episode_length=self.episode_length,
                           episode_terms=self.episode_terms)
+
+    def _setup_init_state(self, init_states, init_state_prob, init_pos_range, init_rpy_range, init_lin_vel_range,
+                          init_ang_vel_range, init_joint_vel):
+        self.init_states = self.init_state = self.init_draws = None
+        ranges = (init_pos_range, init_rpy_range, init_lin_vel_range, init_ang_vel_range)
+        if init_states is None and init_joint_vel is None and all(r is None for r in ranges):
+            return
+        torch = _torch()
+        n, words = self.action_dim, 13 + 2 * self.action_dim
+        bounds = []
+        for name, r in zip(("init_pos_range", "init_rpy_range", "init_lin_vel_range", "init_ang_vel_range"), ranges):
+            r = ((0.0, 0.0),) * 3 if r is None else r
+            if len(r) != 3 or any(len(pair) != 2 for pair in r):
+                raise ValueError(f"{name} must hold three (lo, hi) pairs")
+            bounds += [(ctypes.c_float * 3)(*[float(pair[0]) for pair in r]),
+                       (ctypes.c_float * 3)(*[float(pair[1]) for pair in r])]
+        if init_states is not None:
+            if not isinstance(init_states, torch.Tensor) or init_states.device != self.device:
+                raise TypeError(f"init_states must be a torch tensor on {self.device}")
+            if (init_states.dtype != torch.float32 or init_states.dim() != 2 or init_states.shape[0] < 1 or
+                    init_states.shape[1] != words or not init_states.is_contiguous()):
+                raise TypeError(f"init_states must be a contiguous {torch.float32} tensor of shape [K >= 1, {words}]")
+            self.init_states = init_states      # kept: the launches read it at every reset
+        self.init_state = self._info["init_state"] = self._zeros(self.n_worlds, words)
+        self.init_draws = self._info["init_draws"] = self._zeros(self.n_worlds, 13 + n)
+        ic = N.MwFloatInitConfig(*bounds, 0.0 if init_joint_vel is None else init_joint_vel, init_state_prob,
+                                 0 if init_states is None else init_states.shape[0])
+        N.check(N.lib().mw_floatenv_init_state(self._h, ctypes.byref(ic), _ptr(self.init_states),
+                                               _ptr(self.init_state), _ptr(self.init_draws)),
+                "mw_floatenv_init_state")
 
     def _noise_vector(self, obs_noise) -> np.ndarray:
         """obs_noise (group name -> amplitude, or obs_dim values) as the float32 vector the library takes."""

@@ -182,6 +182,23 @@ class MwFloatShapeConfig(ctypes.Structure):
     ]
 
 
+class MwFloatInitConfig(ctypes.Structure):
+    """mw_float_init_config (include/mwstep.h)."""
+    _fields_ = [
+        ("pos_lo", ctypes.c_float * 3),
+        ("pos_hi", ctypes.c_float * 3),
+        ("rpy_lo", ctypes.c_float * 3),
+        ("rpy_hi", ctypes.c_float * 3),
+        ("lin_vel_lo", ctypes.c_float * 3),
+        ("lin_vel_hi", ctypes.c_float * 3),
+        ("ang_vel_lo", ctypes.c_float * 3),
+        ("ang_vel_hi", ctypes.c_float * 3),
+        ("joint_vel", ctypes.c_float),
+        ("state_prob", ctypes.c_float),
+        ("n_states", ctypes.c_int32),
+    ]
+
+
 # (name, restype, argtypes) of every symbol in include/mwstep.h
 _P = ctypes.c_void_p
 _I = ctypes.c_int32
@@ -284,6 +301,7 @@ SIGNATURES = [
     ("mw_floatenv_noise", ctypes.c_int, [_P, ctypes.POINTER(MwFloatNoiseConfig), ctypes.POINTER(ctypes.c_float),
                                          _P, _P, _P]),
     ("mw_floatenv_shaping", ctypes.c_int, [_P, ctypes.POINTER(MwFloatShapeConfig), _P, _P, _P, _P, _P]),
+    ("mw_floatenv_init_state", ctypes.c_int, [_P, ctypes.POINTER(MwFloatInitConfig), _P, _P, _P]),
 ]
 
 # include/mwscene.h

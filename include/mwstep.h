@@ -830,6 +830,78 @@ typedef struct {
 int mw_floatenv_shaping(mw_vecenv* env, const mw_float_shape_config* cfg, float* terms_dev, float* torque_dev,
                         float* ep_return_dev, int32_t* ep_length_dev, float* ep_terms_dev);
 
+/* Initial-state randomisation and a reset-state bank of a floating-base env:
+ * where an episode starts is drawn on the device by the launch that issues the
+ * reset (the post launch, and mw_vecenv_reset's), inside the step's three
+ * launches (no host copy, capturable).  Off unless configured, and with it off
+ * every output is what it was.  Call it after mw_floatenv_create and before the
+ * first mw_vecenv_reset (MW_ESTATE after it, or on another kind of env), in any
+ * order with the other configure calls.  A refused call leaves the env as it
+ * was; a config of all zeros without a bank and without output buffers returns
+ * it as made.
+ *   base row 13 + 2 n float32 words in the layout of a row of obs: base
+ *            position (3), quaternion wxyz (4), world linear (3) and angular
+ *            (3) velocity, q (n), qd (n) -- a recorded observation row is a
+ *            valid row.  Without a bank it is the home row: home_base, zeros,
+ *            home_q, zeros.  With n_states = K > 0, states_dev float32 [K, 13 +
+ *            2 n] is a caller-owned device buffer that must outlive the env;
+ *            with r word 0 and 1 of block 0x40000300 of the counter (global
+ *            world, episode, block, 0) mw_floatenv_randomize describes, an
+ *            episode starts from row r[0] % K where (r[1] >> 8) 2^-24 <
+ *            state_prob, else from the home row.  The rows are read through
+ *            the pointer at every reset: rows overwritten on the env's stream
+ *            between two steps are what the next resets see.  Their content is
+ *            the caller's: a zero quaternion or a non-finite word gives a
+ *            non-finite state, which the run flags diverged, so that the next
+ *            step ends the episode and resets the world.
+ *   draws    on top of the row, each group off when all its bounds are zero;
+ *            U(lo, hi) is lo + (hi - lo) (x >> 8) 2^-24 of one Philox word:
+ *              block 0x40000301  words 0..2: offsets added to the base position
+ *                                (pos_lo / pos_hi, m, world frame)
+ *              block 0x40000302  words 0..2: roll, pitch, yaw (rpy_lo / rpy_hi,
+ *                                rad); the orientation becomes qz(yaw) qy(pitch)
+ *                                qx(roll) q_row -- world-frame rotations after
+ *                                the row's own -- normalised in float32.  With
+ *                                the group off the row's quaternion is written
+ *                                as it is (the run normalises what it takes)
+ *              block 0x40000303  words 0..2: added to the world linear velocity
+ *                                (lin_vel_lo / lin_vel_hi, m/s)
+ *              block 0x40000304  words 0..2: added to the world angular velocity
+ *                                (ang_vel_lo / ang_vel_hi, rad/s)
+ *              block 0x40000340 | d / 4, word d % 4: U(-joint_vel, joint_vel)
+ *                                added to qd of joint d (rad/s)
+ *            Joint positions are row_q + U(-joint_noise, joint_noise) clipped
+ *            into the position limits: the draw of mw_floatenv_create (blocks 0
+ *            .. (n + 3) / 4 - 1) with row_q in the place of home_q.  No other
+ *            draw of the env changes.
+ *   reset    the reset row of obs is the observation of the drawn state (in the
+ *            locomotion task the projected gravity and the body-frame
+ *            velocities too), and joint_acc of the shaping terms is taken from
+ *            the drawn qd on an episode's first step.  Nothing checks a drawn
+ *            state against z_min, cos_tilt_max or the ground: a start beyond
+ *            them ends at the next step, a start below the ground is the
+ *            caller's to avoid through the ranges.
+ * state_dev float32 [n_worlds, 13 + 2 n] (the state the current episode started
+ * from: the first 13 + 2 n words of the clean reset row) and draws_dev float32
+ * [n_worlds, 13 + n] (the position offsets, roll pitch yaw, the linear and the
+ * angular velocity offsets, the bank row as a float -- -1 the home row -- and
+ * the n joint-velocity draws) are caller-owned device buffers (each may be NULL)
+ * that must outlive the env; a world's rows are written by every reset of it.
+ * MW_EINVAL: a non-finite bound or lo > hi, joint_vel < 0 or non-finite,
+ * state_prob outside [0, 1], n_states < 0, n_states > 0 with states_dev NULL
+ * or n_states == 0 with states_dev given. */
+typedef struct {
+    float pos_lo[3], pos_hi[3];         /* m, world frame                       */
+    float rpy_lo[3], rpy_hi[3];         /* rad: roll, pitch, yaw                */
+    float lin_vel_lo[3], lin_vel_hi[3]; /* m/s, world frame                     */
+    float ang_vel_lo[3], ang_vel_hi[3]; /* rad/s, world frame                   */
+    float joint_vel;                    /* rad/s, >= 0                          */
+    float state_prob;                   /* in [0, 1]                            */
+    int32_t n_states;                   /* rows of states_dev, 0 = no bank      */
+} mw_float_init_config;
+int mw_floatenv_init_state(mw_vecenv* env, const mw_float_init_config* cfg, const float* states_dev, float* state_dev,
+                           float* draws_dev);
+
 #ifdef __cplusplus
 }
 #endif

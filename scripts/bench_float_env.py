@@ -68,6 +68,17 @@ again (4), three force words per active contact slot and list that names its
 link (12 S), the twelve running sums read and written (96) and the row of
 terms (40).
 
+--init adds two envs to the alternation whose episodes last INIT_EPISODE
+steps, so that every world resets inside the timed windows: env_ibase, which
+resets to the home state as env does, and env_init, the same with the
+initial-state randomisation on (mw_floatenv_init_state: all four groups of
+draws, the joint-velocity draws and a 256-row bank of perturbed home rows taken
+with probability one half, both output buffers attached) -- the branch of the
+post kernel's reset block that draws where an episode starts -- and reports
+env_init - env_ibase.  The two do not run the same physics after a reset (that
+is the feature), so the difference holds the run kernel's share too; the post
+launch alone is timed by float_env_trace_probe.py --init.
+
 Not a bench.py leg.  Prints one JSON line per model."""
 
 import argparse
@@ -101,7 +112,26 @@ SHAPING = dict(reward_terms=dict(torque=2e-5, power=1e-4, joint_acc=2.5e-7, orie
 SHAPING_LINKS = {"quadruped": dict(termination_links=("trunk",), penalised_links=("trunk",), termination_force=1.0),
                  "icub": dict(termination_links=("l_foot", "r_foot"), penalised_links=("l_foot", "r_foot"),
                               termination_force=1e6)}
+# --init: every group of draws and the joint velocities, small enough that a 20-step episode stays upright
+INIT_EPISODE = 20
+INIT = dict(init_pos_range=((-0.2, 0.2), (-0.2, 0.2), (0.0, 0.02)), init_rpy_range=((-0.05, 0.05), (-0.05, 0.05), (-3.1, 3.1)),
+            init_lin_vel_range=((-0.2, 0.2), (-0.2, 0.2), (-0.05, 0.05)),
+            init_ang_vel_range=((-0.2, 0.2), (-0.2, 0.2), (-0.2, 0.2)), init_joint_vel=0.2, init_state_prob=0.5)
+INIT_BANK_ROWS = 256
 sys.path.insert(0, os.path.join(ROOT, "gym-ignition_amd", "python"))
+
+
+def init_bank(torch, env, rows=INIT_BANK_ROWS, seed=0):
+    """A bank of `rows` start states on the env's device: the home row with the
+    joints within 0.05 rad of the home posture, moving at up to 0.1 rad/s."""
+    import numpy as np
+    n = env.action_dim
+    rng = np.random.default_rng(seed)
+    bank = np.zeros((rows, 13 + 2 * n), np.float32)
+    bank[:, :7] = env.home_base
+    bank[:, 13:13 + n] = env.home_q + rng.uniform(-0.05, 0.05, (rows, n))
+    bank[:, 13 + n:] = rng.uniform(-0.1, 0.1, (rows, n))
+    return torch.from_numpy(bank).to(env.device)
 
 
 def capture(torch, stream, fn, warm):
@@ -220,6 +250,16 @@ def measure(torch, args, model, W):
             szeros = torch.zeros((W, shaped.action_dim), dtype=torch.float32, device=shaped.device)
         graphs["env_sbase"] = capture(torch, stream, lambda: sbase.step_raw(szeros.data_ptr()), args.warmup)
         graphs["env_shape"] = capture(torch, stream, lambda: shaped.step_raw(szeros.data_ptr()), args.warmup)
+    ibase = started = None
+    if args.init:
+        with torch.cuda.stream(stream):
+            ibase = getattr(FloatVecEnv, model)(W, max_episode_steps=INIT_EPISODE, z_min=-10.0)
+            ibase.reset()
+            started = getattr(FloatVecEnv, model)(W, max_episode_steps=INIT_EPISODE, z_min=-10.0,
+                                                  init_states=init_bank(torch, env), **INIT)
+            started.reset()
+        graphs["env_ibase"] = capture(torch, stream, lambda: ibase.step_raw(actions.data_ptr()), args.warmup)
+        graphs["env_init"] = capture(torch, stream, lambda: started.step_raw(actions.data_ptr()), args.warmup)
     times = {k: [] for k in graphs}
     for _ in range(args.rounds):
         for k, g in graphs.items():
@@ -318,6 +358,23 @@ def measure(torch, args, model, W):
                     "shape_episodes_finished": int(shaped.counters()[0].sum().item())})
         sbase.close()
         shaped.close()
+    if started is not None:
+        n = env.action_dim
+        draws = started.init_draws.cpu().numpy()
+        zs = started.sim.base_pose()[:, 2]
+        out.update({"env_ibase_step_us": round(med["env_ibase"], 3), "env_init_step_us": round(med["env_init"], 3),
+                    "init_minus_ibase_us": round(med["env_init"] - med["env_ibase"], 3),
+                    "ibase_minus_env_us": round(med["env_ibase"] - med["env"], 3),
+                    "init": {k: v for k, v in INIT.items()}, "init_bank_rows": INIT_BANK_ROWS,
+                    "init_episode_steps": INIT_EPISODE,
+                    "init_episodes_finished": int(started.counters()[0].sum().item()),
+                    "ibase_episodes_finished": int(ibase.counters()[0].sum().item()),
+                    "init_bank_starts_in_last_episode": int((draws[:, 12] >= 0).sum()),
+                    "init_output_bytes_per_world_and_reset": 4 * (13 + 2 * n + 13 + n),
+                    "init_bank_bytes_read_per_bank_start": 4 * (13 + 2 * n),
+                    "init_base_z_range_after": [round(float(zs.min()), 4), round(float(zs.max()), 4)]})
+        ibase.close()
+        started.close()
     env.close()
     sim.close()
     return out
@@ -343,6 +400,9 @@ def main():
     p.add_argument("--shaping", action="store_true",
                    help="also time the locomotion env without (env_sbase) and with (env_shape) the shaping terms, "
                         "contact termination and episode statistics")
+    p.add_argument("--init", action="store_true",
+                   help="also time envs whose worlds reset inside the windows: to the home state (env_ibase) and with "
+                        "the initial-state randomisation and a 256-row bank on (env_init)")
     p.add_argument("--task", choices=("forward", "locomotion"), default="forward",
                    help="locomotion: also time an env with the velocity-command task on (env_loco)")
     args = p.parse_args()
