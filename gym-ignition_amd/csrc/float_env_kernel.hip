@@ -43,6 +43,13 @@
 // alone: a done world starts from a row of the caller's bank or the home row
 // plus drawn offsets (init_reset) where the plain reset writes constants, and
 // the first words of the reset rows leave once more as T.init.state_out.
+// The motion-clip tracking task (mw_floatenv_tracking) is the fourth
+// (T.track.on): one wave works out every world's frame clock, the waves then
+// blend the worlds' reference rows out of the caller's clips into one more LDS
+// tile -- a wave per row, its lanes across the row's words, so the clip is read
+// as contiguous spans -- and wave 0 takes the five errors lane-per-world from
+// it (track_clock, track_stage); the reset block starts a done world from a row
+// of a drawn clip through init_reset.
 //
 // Both kernels are transposes between the row-major [W, k] tensors of the
 // agent and the [k][W] SoA arrays of the simulator.  A block of 256 threads
@@ -55,6 +62,7 @@
 #include <hip/hip_runtime.h>
 
 #include <array>
+#include <mutex>
 #include <utility>
 
 #include "finite.hpp"
@@ -73,6 +81,31 @@ constexpr int kShapePitch = kShapeTerms | 1;  // rows of the [kEnvTile][10] tile
 // dynamic LDS of the post kernel's shaping branch: partial sums, two term tiles, hits
 constexpr size_t kShapeLds = (kEnvWaves * kShapeSums * kEnvTile + 2 * kEnvTile * kShapePitch) * sizeof(float) +
                              kEnvWaves * kEnvTile;
+
+// dynamic LDS of the post kernel's tracking branch, behind the shaping region
+// where there is one: the reference tile [kEnvTile][track_pitch(n)] -- a row is
+// the 13 + 2 n blended words, with q0 unblended in the quaternion's place, and
+// q1 in four more words, for the nlerp a lane takes per world -- the two
+// [kEnvTile][5] tiles of terms_out / errors_out (5 is odd already) and
+// kTrackClockWords arrays of one word per world: the clocks.
+constexpr int kTrackClockWords = 10;
+enum TrackClockWord : int {
+    kTcRow0 = 0,  // rows of the caller's buffer the reference of the step's instant x_t lies between
+    kTcRow1,
+    kTcBlend,     // (float) its blend
+    kTcWraps,     // periods of a looping clip gone by
+    kTcFirst,     // the clip's first and last row: the displacement of a period
+    kTcLast,
+    kTcNext0,     // likewise for x_{t+1}, the reference joint positions of the observation
+    kTcNext1,
+    kTcNextBlend,
+    kTcEnded,     // the clip ended: the episode is truncated
+};
+__host__ __device__ constexpr int track_pitch(int n) { return (13 + 2 * n + 4) | 1; }
+__host__ __device__ constexpr size_t track_lds(int n) {
+    return (static_cast<size_t>(kEnvTile) * track_pitch(n) + 2 * kEnvTile * kTrackTerms + kTrackClockWords * kEnvTile) *
+           sizeof(float);
+}
 
 // actions [W, n] -> out [n][W] (SimDev::cmd or ptgt), and sum_i a_i^2 per
 // world for the reward (asq [W]).  The value stored is the float32 the host
@@ -354,6 +387,76 @@ __device__ __forceinline__ void shape_terms(const FloatShapeF& H, const float* p
     ft_shape_terms(H, x, diverged, term);
 }
 
+// The frame clocks of one world of the tracking task (lane = world, one wave):
+// from the steps taken before this launch's update and the kept start frame,
+// the instant the step's state is compared at (t = steps + 1) and the next one
+// (the reference joint positions of the observation), as rows of the caller's
+// buffer and blends in LDS for the staging waves; the phase and clip words go
+// straight into the world's row of the obs tile.
+__device__ __forceinline__ void track_clock(const FloatTrackF& K, uint32_t steps, int w, int lane, float* row,
+                                            uint32_t* s_clock) {
+    const int32_t c = K.clip[w], f0 = K.f0[w];
+    const int32_t* __restrict__ e = K.table + c * kTrackTableWords;
+    const int32_t first = e[0], length = e[1];
+    const bool loop = e[2] != 0;
+    const TrackClock A = ft_track_clock(f0, steps + 1u, K.frame_num, K.frame_den, length, loop);
+    const TrackClock B = ft_track_clock(f0, steps + 2u, K.frame_num, K.frame_den, length, loop);
+    s_clock[kTcRow0 * kEnvTile + lane] = static_cast<uint32_t>(first + A.i);
+    s_clock[kTcRow1 * kEnvTile + lane] = static_cast<uint32_t>(first + A.i1);
+    s_clock[kTcBlend * kEnvTile + lane] = __float_as_uint(A.a);
+    s_clock[kTcWraps * kEnvTile + lane] = A.wraps;
+    s_clock[kTcFirst * kEnvTile + lane] = static_cast<uint32_t>(first);
+    s_clock[kTcLast * kEnvTile + lane] = static_cast<uint32_t>(first + length - 1);
+    s_clock[kTcNext0 * kEnvTile + lane] = static_cast<uint32_t>(first + B.i);
+    s_clock[kTcNext1 * kEnvTile + lane] = static_cast<uint32_t>(first + B.i1);
+    s_clock[kTcNextBlend * kEnvTile + lane] = __float_as_uint(B.a);
+    s_clock[kTcEnded * kEnvTile + lane] = A.ended ? 1u : 0u;
+    float sn, cs;
+    ft_track_phase_words(ft_track_phase(A.i, A.a, length), sn, cs);
+    row[K.nb] = sn;
+    row[K.nb + 1] = cs;
+    row[K.nb + 2] = static_cast<float>(c);
+}
+
+// The reference rows of the tile's worlds staged into LDS: a wave takes row r
+// with its lanes across the row's words, so every load of the clip is a
+// contiguous span of one row (two rows per world, and two words of two more
+// where a looping clip has wrapped).  The quaternion's words are kept apart
+// (track_lds); the n joint positions of x_{t+1} go straight into the obs tile.
+__device__ __forceinline__ void track_stage(const FloatTrackF& K, int n, int rows, int wave, int lane, float* s_ref,
+                                            const uint32_t* s_clock, float* tile, int pitch) {
+    const int NS = 13 + 2 * n, RP = track_pitch(n);
+    const float* __restrict__ clips = K.clips;
+    for (int r = wave; r < rows; r += kEnvWaves) {
+        const float* __restrict__ c0 = clips + static_cast<size_t>(s_clock[kTcRow0 * kEnvTile + r]) * NS;
+        const float* __restrict__ c1 = clips + static_cast<size_t>(s_clock[kTcRow1 * kEnvTile + r]) * NS;
+        const float a = __uint_as_float(s_clock[kTcBlend * kEnvTile + r]);
+        const uint32_t wraps = s_clock[kTcWraps * kEnvTile + r];
+        float* ref = s_ref + r * RP;
+        for (int k = lane; k < NS; k += 64) {
+            const float p0 = c0[k], p1 = c1[k];
+            if (k >= 3 && k < 7) {
+                ref[k] = p0;
+                ref[NS + k - 3] = p1;
+                continue;
+            }
+            float v = ft_track_lerp(p0, p1, a);
+            if (k < 2 && wraps) {
+                const float* __restrict__ cl = clips + static_cast<size_t>(s_clock[kTcLast * kEnvTile + r]) * NS;
+                const float* __restrict__ cf = clips + static_cast<size_t>(s_clock[kTcFirst * kEnvTile + r]) * NS;
+                v = ft_track_wrapped(v, wraps, cl[k], cf[k]);
+            }
+            ref[k] = v;
+        }
+        if (K.obs_reference) {
+            const float* __restrict__ b0 = clips + static_cast<size_t>(s_clock[kTcNext0 * kEnvTile + r]) * NS + 13;
+            const float* __restrict__ b1 = clips + static_cast<size_t>(s_clock[kTcNext1 * kEnvTile + r]) * NS + 13;
+            const float b = __uint_as_float(s_clock[kTcNextBlend * kEnvTile + r]);
+            for (int k = lane; k < n; k += 64) tile[r * pitch + K.nb + 3 + k] = ft_track_lerp(b0[k], b1[k], b);
+        }
+    }
+}
+
 // The reset of one done world with the initial-state randomisation on
 // (mw_floatenv_init_state, T.init.on; lane = world, called by every wave of the
 // lane): it takes the place of the plain reset's joint loop and base block and
@@ -378,6 +481,13 @@ __device__ __forceinline__ void shape_terms(const FloatShapeF& H, const float* p
 // it, behind the barriers that follow the gather's store of the same word.  A
 // non-finite q of a bank row stays non-finite (the clip alone would turn a NaN
 // into the lower limit): the run flags the world diverged.
+// With the tracking task on (T.track.on) the base row is a row of a clip: every
+// wave that has work draws the clip and the start frame from the tracking block
+// as it would draw the bank row, and the base wave writes the phase and clip
+// words of x_0 and keeps the world's clip and start frame for the clocks of the
+// steps to come.  The reference joint positions of x_1 follow in a pass of
+// their own (track_reset_reference), which draws once more instead of keeping
+// the rows' addresses live across this function.
 constexpr int kInitBaseWave = 2;
 __device__ __forceinline__ void init_reset(const ChainF* __restrict__ P, const FloatTaskF& T, const SimDev& S,
                                            const FreeDev& D, int n, size_t Ws, int w, int wave, uint32_t episode,
@@ -395,6 +505,17 @@ __device__ __forceinline__ void init_reset(const ChainF* __restrict__ P, const F
     }
     // one pointer for either kind of start: the home row is a row in device memory too (the env's own)
     const float* __restrict__ base_row = k_row >= 0 ? I.states + static_cast<size_t>(k_row) * NS : I.home;
+    const FloatTrackF& K = T.track;
+    const bool tracked = K.on != 0u;
+    int32_t clip = 0, f0 = 0;
+    if (tracked) {
+        uint32_t r[4];
+        philox(T.seed_lo, T.seed_hi, g, episode, r, kFtTrackBlock);
+        clip = ft_track_clip(r[0], K.n_clips);
+        const int32_t* __restrict__ e = K.table + clip * kTrackTableWords;
+        f0 = ft_track_start(r[1], r[2], e[1], K.rsi_prob);
+        base_row = K.clips + static_cast<size_t>(e[0] + f0) * NS;
+    }
     float* __restrict__ draws = I.draws_out ? I.draws_out + static_cast<size_t>(w) * (kInitBaseDraws + n) : nullptr;
     const bool jv = I.joint_vel > 0.f;
     for (int b = wave; b < nblocks; b += kEnvWaves) {
@@ -476,6 +597,36 @@ __device__ __forceinline__ void init_reset(const ChainF* __restrict__ P, const F
         for (int k = 0; k < 12; ++k) draws[k] = off[k / 3][k % 3];
         draws[12] = static_cast<float>(k_row);
     }
+    if (tracked) {
+        float sn, cs;
+        ft_track_phase_words(ft_track_phase(f0, 0.f, K.table[clip * kTrackTableWords + 1]), sn, cs);
+        row[K.nb] = sn;
+        row[K.nb + 1] = cs;
+        row[K.nb + 2] = static_cast<float>(clip);
+        K.clip[w] = clip;
+        K.f0[w] = f0;
+        if (K.clip_out) K.clip_out[w] = clip;
+        if (K.frame_out) K.frame_out[w] = f0;
+    }
+}
+
+// The reference joint positions of x_1 in the reset row of one done world
+// (obs_reference; lane = world, the joints round the waves): the gather of two
+// rows' joint words per done lane, as init_reset's of the base row.
+__device__ __forceinline__ void track_reset_reference(const FloatTaskF& T, int n, int w, int wave, uint32_t episode,
+                                                      float* row) {
+    const FloatTrackF& K = T.track;
+    if (wave >= n) return;
+    uint32_t r[4];
+    philox(T.seed_lo, T.seed_hi, T.world_offset + static_cast<uint32_t>(w), episode, r, kFtTrackBlock);
+    const int32_t* __restrict__ e = K.table + ft_track_clip(r[0], K.n_clips) * kTrackTableWords;
+    const int32_t first = e[0], length = e[1];
+    const TrackClock B = ft_track_clock(ft_track_start(r[1], r[2], length, K.rsi_prob), 1u, K.frame_num, K.frame_den,
+                                        length, e[2] != 0);
+    const int NS = 13 + 2 * n;
+    const float* __restrict__ b0 = K.clips + static_cast<size_t>(first + B.i) * NS + 13;
+    const float* __restrict__ b1 = K.clips + static_cast<size_t>(first + B.i1) * NS + 13;
+    for (int d = wave; d < n; d += kEnvWaves) row[K.nb + 3 + d] = ft_track_lerp(b0[d], b1[d], B.a);
 }
 
 // Per world: gather the observation, reward, done, counters; where done, the
@@ -528,6 +679,15 @@ __device__ __forceinline__ void init_reset(const ChainF* __restrict__ P, const F
 // off draws nothing and a joint outside the mask leaves its record alone; both
 // report the nominal words and the draws 0, 0, 1 (T.joints.joints_out,
 // draw_out).  The joints go round the waves starting at wave 1.
+// Tracking (mw_floatenv_tracking, T.track.on; block-uniform like shaping): the
+// row grows by 3 words behind everything else -- sin and cos of the phase and
+// the clip, written by wave 1 with the clocks -- and, with obs_reference, n
+// reference joint positions.  Wave 1 works out the clocks before the counters
+// move, a barrier of this branch alone hands them to the staging (track_stage),
+// and behind the gather's barrier wave 0 takes the errors from the reference
+// tile, ors the early termination into the termination and the clip's end into
+// done, and adds the five terms to the reward ahead of the shaping terms, so
+// that the episode return of the shaping statistics includes them.
 template <bool RAND, bool PUSH, bool LOCO, bool INERT, bool JOINT>
 __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const ChainF* __restrict__ P, FloatTaskF T,
                                                                      SimDev S, FreeDev D, VecDev V,
@@ -555,6 +715,13 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
     float* const s_terms = s_part + kEnvWaves * kShapeSums * kEnvTile;
     float* const s_epterms = s_terms + kEnvTile * kShapePitch;
     uint8_t* const s_hit = reinterpret_cast<uint8_t*>(s_epterms + kEnvTile * kShapePitch);
+    // tracking (block-uniform; the launcher adds track_lds(n) bytes behind the
+    // shaping region, or behind the tile without one, only then)
+    const bool tracked = __builtin_expect(T.track.on != 0u, 0);
+    float* const s_ref = s_part + (shaped ? kShapeLds / sizeof(float) : 0);
+    float* const s_tterms = s_ref + kEnvTile * track_pitch(n);
+    float* const s_terrs = s_tterms + kEnvTile * kTrackTerms;
+    uint32_t* const s_clock = reinterpret_cast<uint32_t*>(s_terrs + kEnvTile * kTrackTerms);
     const int NB = 13 + 2 * n + T.n_links;  // LOCO: the appended block starts here
     const int w0 = blockIdx.x * kEnvTile;
     const int rows = min(kEnvTile, W - w0);
@@ -572,6 +739,11 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
                 const int r = i / n, d = i - r * n;
                 tile[r * pitch + NB + 12 + d] = kept[i];
             }
+        }
+        if (tracked) {
+            if (wave == 1 && live) track_clock(T.track, V.steps[w], w, lane, row, s_clock);
+            __syncthreads();
+            track_stage(T.track, n, rows, wave, lane, s_ref, s_clock, tile, pitch);
         }
         // gather: lane = world, the waves split the words
         if (live) {
@@ -638,8 +810,21 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
 #pragma unroll
                     for (int v = 0; v < kEnvWaves; ++v) term = term || s_hit[v * kEnvTile + lane] != 0;
                 }
+                float tr_err[kTrackTerms] = {0.f, 0.f, 0.f, 0.f, 0.f};
+                bool clip_end = false;
+                if (tracked) {
+                    const int NS = 13 + 2 * n;
+                    const float* ref = s_ref + lane * track_pitch(n);
+                    const float q0[4] = {ref[3], ref[4], ref[5], ref[6]};
+                    const float q1[4] = {ref[NS], ref[NS + 1], ref[NS + 2], ref[NS + 3]};
+                    float qr[4];
+                    ft_track_nlerp(q0, q1, __uint_as_float(s_clock[kTcBlend * kEnvTile + lane]), qr);
+                    ft_track_errors(row, ref, qr, T.track.wj, n, T.track.ang_scale, tr_err);
+                    term = term || ft_track_failed(T.track, tr_err);
+                    clip_end = s_clock[kTcEnded * kEnvTile + lane] != 0u;  // truncated, as at the time limit
+                }
                 uint32_t steps = V.steps[w] + 1u;
-                done = term || (T.max_steps > 0 && steps >= static_cast<uint32_t>(T.max_steps));
+                done = term || clip_end || (T.max_steps > 0 && steps >= static_cast<uint32_t>(T.max_steps));
                 float rew = ft_reward(T, term, row[7], asq[w], ft_sum_sq_diff(row + 13, 1, T.home_q, n));
                 if constexpr (LOCO) {
                     const float cmd[3] = {s_cmd[lane], s_cmd[kEnvTile + lane], s_cmd[2 * kEnvTile + lane]};
@@ -648,6 +833,16 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
                     float pay = 0.f;
                     for (int j = 0; j < T.n_links; ++j) pay += s_pay[j * kEnvTile + lane];
                     rew = ft_loco_reward(T.loco, rew, cmd, v, om, T.loco.action_rate[w], pay);
+                }
+                if (tracked) {
+                    float tr_term[kTrackTerms];
+                    ft_track_terms(T.track, tr_err, S.div[w] != 0, tr_term);
+                    rew = ft_track_reward(rew, tr_term);
+#pragma unroll
+                    for (int k = 0; k < kTrackTerms; ++k) {
+                        s_tterms[lane * kTrackTerms + k] = tr_term[k];
+                        s_terrs[lane * kTrackTerms + k] = tr_err[k];
+                    }
                 }
                 if (shaped) {
                     const FloatShapeF& H = T.shape;
@@ -712,6 +907,16 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
                 if (ep_terms && s_done[r]) ep_terms[o] = s_epterms[r * kShapePitch + k];
             }
         }
+        if (tracked) {
+            // likewise [rows, 5]
+            float* __restrict__ terms_out = T.track.terms_out;
+            float* __restrict__ errors_out = T.track.errors_out;
+            for (int i = threadIdx.x; i < rows * kTrackTerms; i += kEnvThreads) {
+                const size_t o = static_cast<size_t>(w0) * kTrackTerms + i;
+                if (terms_out) terms_out[o] = s_tterms[i];
+                if (errors_out) errors_out[o] = s_terrs[i];
+            }
+        }
         __syncthreads();
     } else {
         if (wave == 0) {
@@ -759,6 +964,7 @@ __global__ void __launch_bounds__(kEnvThreads) float_env_post_kernel(const Chain
         const uint32_t episode = s_episode[lane];
         if (starts) {
             init_reset(P, T, S, D, n, Ws, w, wave, episode, shaped, LOCO ? NB : -1, row);
+            if (tracked && T.track.obs_reference) track_reset_reference(T, n, w, wave, episode, row);
         } else {
             for (int b = wave; b < (n + 3) / 4; b += kEnvWaves) {
                 uint32_t r[4];
@@ -994,16 +1200,51 @@ constexpr std::array<PostKernel, sizeof...(I)> post_kernels(std::index_sequence<
 }
 constexpr auto kPostKernels = post_kernels(std::make_index_sequence<32>{});
 
+// dynamic LDS of the post launch: the tile of rows, then the shaping and the tracking region where on
+static size_t post_dynamic_lds(const FloatTaskF& T, int n) {
+    return static_cast<size_t>(dev::kEnvTile) * (T.n_obs | 1) * sizeof(float) + (T.shape.on ? dev::kShapeLds : 0) +
+           (T.track.on ? dev::track_lds(n) : 0);
+}
+
+hipError_t reserve_float_env_post_lds(const FloatTaskF& T, int n, int device, size_t* need, size_t* limit) {
+    const size_t dynamic = post_dynamic_lds(T, n);
+    const size_t loco = T.loco.on ? 4u : 0u;  // the instances with the locomotion arrays in their static LDS
+    hipFuncAttributes fa{};
+    if (hipError_t err = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(kPostKernels[loco]))) return err;
+    int per_block = 0;
+    if (hipError_t err = hipDeviceGetAttribute(&per_block, hipDeviceAttributeMaxSharedMemoryPerBlock, device)) return err;
+    *need = dynamic + fa.sharedSizeBytes;
+    *limit = static_cast<size_t>(per_block);
+    if (*need > *limit || *need <= 65536u) return hipSuccess;
+    // beyond the default: every instance this env can still become (the other
+    // four flags may follow) is told how much dynamic LDS it may be launched
+    // with.  The attribute belongs to the kernel, not to the env: it is only
+    // ever raised, so that an env configured earlier keeps what it was given.
+    static std::mutex guard;
+    static size_t granted[2] = {0u, 0u};
+    const std::lock_guard<std::mutex> lock(guard);
+    if (dynamic <= granted[loco ? 1 : 0]) return hipSuccess;
+    for (size_t i = 0; i < kPostKernels.size(); ++i)
+        if ((i & 4u) == loco)
+            if (hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kPostKernels[i]),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     static_cast<int>(dynamic)))
+                return err;
+    granted[loco ? 1 : 0] = dynamic;
+    return hipSuccess;
+}
+
 hipError_t launch_float_env_post(const ChainF* P, const FloatTaskF& T, const SimDev& S, const FreeDev& D,
                                  const VecDev& V, const float* asq, float* obs, float* reward, uint8_t* done,
                                  float* term_obs, int n, int W, int reset_all, hipStream_t st) {
-    const size_t lds = static_cast<size_t>(dev::kEnvTile) * (T.n_obs | 1) * sizeof(float) +
-                       (T.shape.on ? dev::kShapeLds : 0);
+    const size_t lds = post_dynamic_lds(T, n);
     const dim3 grid((W + dev::kEnvTile - 1) / dev::kEnvTile), block(dev::kEnvThreads);
     // The locomotion rows are 25 + 3 n + n_links words: at most (48 dofs, 8
     // links) 64 x 177 words = 45,312 B, with the 14,080 B of the shaping branch
     // (partials, term tiles, hits) and the kernel's 3,648 B of static LDS still
-    // inside the 65,536 B a block gets without asking for more.
+    // inside the 65,536 B a block gets without asking for more.  The tracking
+    // task adds its reference tile (track_lds) and can pass that: the configure
+    // calls have then run reserve_float_env_post_lds.
     const bool rand = T.rand.friction_hi > 0.f, push = T.rand.push_interval > 0u, loco = T.loco.on != 0u;
     const bool inert = T.inertia.wpar != nullptr, joint = T.joints.wpar != nullptr;
     hipLaunchKernelGGL(kPostKernels[rand | push << 1 | loco << 2 | inert << 3 | joint << 4], grid, block, lds, st, P, T,

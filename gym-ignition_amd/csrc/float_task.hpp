@@ -20,7 +20,9 @@
 // accumulator step), built by tests/host_float_shape/harness.cpp, and that of
 // the initial-state randomisation (mw_floatenv_init_state: the row choice, the
 // offsets, the composed orientation, the velocity sums), built by
-// tests/host_float_init/harness.cpp.
+// tests/host_float_init/harness.cpp, and that of the motion-clip tracking task
+// (mw_floatenv_tracking: the frame clock, the clip draw, the blended reference
+// row, the five errors and terms), built by tests/host_float_track/harness.cpp.
 #pragma once
 
 #ifdef MW_HOST_TEST
@@ -210,6 +212,46 @@ constexpr uint32_t kFtInitLinBlock = 0x40000303u;  // r[0..2]: linear velocity o
 constexpr uint32_t kFtInitAngBlock = 0x40000304u;  // r[0..2]: angular velocity offsets
 constexpr uint32_t kFtInitQdBlock = 0x40000340u;   // | d / 4, word d % 4: velocity draw of joint d < 48
 
+// Motion-clip tracking task of the floating-base env (mw_floatenv_tracking),
+// off when `on` is zero.  A clip is a run of rows of the caller's buffer, each
+// 13 + 2 n words in the layout of a row of obs; a world follows one clip per
+// episode from a drawn start frame, on an integer frame clock of frame_num /
+// frame_den frames per control step.  What a lane indexes by its own clip --
+// the table -- and what a loop walks -- the joint weights -- sit in device
+// memory, not in this by-value struct: a struct indexed per lane is copied to
+// scratch (see init_reset).
+constexpr int kMaxClips = 16;
+constexpr int kTrackTerms = 5;
+constexpr int kTrackTableWords = 4;  // first row, length, loop, 0 per clip
+enum TrackTerm : int {
+    kTrPose = 0,   // sum_d wj_d (q_d - q^_d)^2
+    kTrVelocity,   // sum_d wj_d (qd_d - qd^_d)^2
+    kTrRootPos,    // |p - p^|^2
+    kTrRootRot,    // 1 - (q . q^)^2
+    kTrRootVel,    // |v - v^|^2 + ang_scale |w - w^|^2
+};
+struct FloatTrackF {
+    uint32_t on;
+    int32_t n_clips;               // 1 .. kMaxClips
+    int32_t frame_num, frame_den;  // frames per control step, both >= 1
+    int32_t obs_reference;         // the block of obs carries the n reference joint positions of the next step
+    int32_t nb;                    // first word of the block in a row of obs: phase sin, cos, clip id, [reference]
+    float rsi_prob;                // a drawn start frame where U(0, 1) of r[2] < rsi_prob, else frame 0
+    float ang_scale;               // weight of the angular part of root_vel
+    float weight[kTrackTerms], scale[kTrackTerms];  // term k = weight[k] expf(-scale[k] e_k)
+    float max_pose, max_root_pos, max_root_rot;     // early termination above it, 0 = off
+    const float* clips;            // [F, 13 + 2 n] the clip rows (caller's, read at every step)
+    const int32_t* table;          // [n_clips][kTrackTableWords] (the env's own, device)
+    const float* wj;               // [n] the per-joint weights (the env's own, device)
+    int32_t* clip;                 // [W] the clip of the current episode (the env's own)
+    int32_t* f0;                   // [W] its start frame
+    float* terms_out;              // [W, 5] the step's signed terms (caller's, may be null)
+    float* errors_out;             // [W, 5] the step's errors (caller's, may be null)
+    int32_t* clip_out;             // [W] copies of clip / f0 (caller's, each may be null)
+    int32_t* frame_out;            // [W]
+};
+constexpr uint32_t kFtTrackBlock = 0x40000400u;  // r[0]: clip, r[1]: start frame, r[2]: drawn start or frame 0
+
 // Task description of the floating-base env (kernel argument, by value).
 struct FloatTaskF {
     int32_t action_mode;     // 0 torque (SimDev::cmd), 1 position (SimDev::ptgt)
@@ -230,6 +272,7 @@ struct FloatTaskF {
     FloatJointF joints;
     FloatNoiseF noise;
     FloatShapeF shape;
+    FloatTrackF track;
     FloatInitF init;
 };
 
@@ -723,6 +766,170 @@ __device__ __forceinline__ void ft_init_base(const FloatInitF& I, const float (&
         for (int k = 0; k < 4; ++k) base[3 + k] = qn[k] = q_row[k];
         ft_init_normalise(qn);
     }
+}
+
+// ---- motion-clip tracking task (FloatTrackF) ----
+
+// The clip of an episode and the frame it starts at, from words 0..2 of its
+// tracking block: clip r0 % n_clips; frame r1 % (length - 1) where U(0, 1) of r2
+// (an exact float32) is below rsi_prob, else 0.  A start frame is never the last
+// row: a looping clip's last row is its first pose again, a clip that ends has
+// nothing to follow from there.
+__device__ __forceinline__ int32_t ft_track_clip(uint32_t r0, int32_t n_clips) {
+    return static_cast<int32_t>(r0 % static_cast<uint32_t>(n_clips));
+}
+__device__ __forceinline__ int32_t ft_track_start(uint32_t r1, uint32_t r2, int32_t length, float rsi_prob) {
+    if (!(ft_unif(r2, 0.f, 1.f) < rsi_prob)) return 0;
+    return static_cast<int32_t>(r1 % static_cast<uint32_t>(length - 1));
+}
+
+// The frame clock, integers throughout: with f0 the start frame and t the steps
+// taken, x_num = f0 den + t num; the reference of that instant lies between
+// rows i and i1 of the clip at blend a = (x_num % den) / den, i = x_num / den.
+// A looping clip has the period length - 1 (its last row is its first pose):
+// i wraps modulo the period and `wraps` counts the periods gone by.  A clip
+// that ends is `ended` at the first instant that would need a row beyond the
+// last; the reference then stays the last row (i = i1 = length - 1, a = 0).
+// With a == 0 the second row is not needed and i1 = i, so no row beyond the
+// clip is ever addressed.
+struct TrackClock {
+    int32_t i, i1;   // rows of the clip, 0 <= i <= i1 <= length - 1
+    float a;         // in [0, 1)
+    uint32_t wraps;
+    bool ended;
+};
+__device__ __forceinline__ TrackClock ft_track_clock(int32_t f0, uint32_t t, int32_t num, int32_t den, int32_t length,
+                                                     bool loop) {
+    const uint64_t d = static_cast<uint64_t>(den);
+    const uint64_t x = static_cast<uint64_t>(f0) * d + static_cast<uint64_t>(t) * static_cast<uint64_t>(num);
+    const uint64_t last = static_cast<uint64_t>(length - 1);
+    // the same quotients in 32 bits where x fits, as it does for all but the longest
+    // episodes: a 64-bit division is a long routine on the device
+    const bool narrow = (x >> 32) == 0u;
+    uint64_t fi = narrow ? static_cast<uint32_t>(x) / static_cast<uint32_t>(den) : x / d;
+    const uint32_t rem = static_cast<uint32_t>(x - fi * d);
+    TrackClock c;
+    c.wraps = 0u;
+    c.ended = false;
+    c.a = static_cast<float>(rem) / static_cast<float>(den);
+    if (loop) {
+        const uint64_t w = narrow ? static_cast<uint32_t>(fi) / static_cast<uint32_t>(last) : fi / last;
+        c.wraps = static_cast<uint32_t>(w);
+        fi -= w * last;
+    } else if (fi + (rem ? 1u : 0u) > last) {
+        c.ended = true;
+        fi = last;
+        c.a = 0.f;
+    }
+    c.i = static_cast<int32_t>(fi);
+    c.i1 = c.i + ((rem && !c.ended) ? 1 : 0);
+    return c;
+}
+
+// phi = x_t / (length - 1), modulo 1 on a looping clip: two roundings
+__device__ __forceinline__ float ft_track_phase(int32_t i, float a, int32_t length) {
+    MW_FT_NO_CONTRACT
+    const float x = static_cast<float>(i) + a;
+    return x / static_cast<float>(length - 1);
+}
+// sin and cos of 2 pi phi: one rounding of the angle, then sinf / cosf
+__device__ __forceinline__ void ft_track_phase_words(float phi, float& s, float& c) {
+    MW_FT_NO_CONTRACT
+    const float ang = 6.283185307179586f * phi;
+    s = sinf(ang);
+    c = cosf(ang);
+}
+
+// One word of the reference row: p0 + a (p1 - p0), the difference rounded, then
+// one fused step; a == 0 gives p0's bits.
+__device__ __forceinline__ float ft_track_lerp(float p0, float p1, float a) {
+    MW_FT_NO_CONTRACT
+    const float d = p1 - p0;
+    return fmaf(a, d, p0);
+}
+// The base x or y of a looping clip after `wraps` periods: the word plus wraps
+// times the clip's displacement over a period (last row minus first row)
+__device__ __forceinline__ float ft_track_wrapped(float word, uint32_t wraps, float p_last, float p_first) {
+    MW_FT_NO_CONTRACT
+    const float d = p_last - p_first;
+    return fmaf(static_cast<float>(wraps), d, word);
+}
+// The reference orientation: nlerp of q0 and q1 (wxyz) -- q1 negated where the
+// dot product is negative (the short way round), every word blended as above,
+// the result normalised (ft_init_normalise).
+__device__ __forceinline__ void ft_track_nlerp(const float (&q0)[4], const float (&q1)[4], float a, float (&q)[4]) {
+    MW_FT_NO_CONTRACT
+    const float ww = q0[0] * q1[0];
+    const float wx = fmaf(q0[1], q1[1], ww);
+    const float wy = fmaf(q0[2], q1[2], wx);
+    const float dot = fmaf(q0[3], q1[3], wy);
+    const float sgn = dot < 0.f ? -1.f : 1.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = ft_track_lerp(q0[k], sgn * q1[k], a);
+    ft_init_normalise(q);
+}
+
+// The five errors of a world: row, the 13 + 2 n first words of its observation
+// (the state after the step); ref, the reference row of the same instant with
+// its orientation already blended (qr).  Sums run in index order, each item a
+// difference, a weighted product and a fused step.
+__device__ __forceinline__ void ft_track_errors(const float* row, const float* ref, const float (&qr)[4],
+                                                const float* wj, int n, float ang_scale, float (&e)[kTrackTerms]) {
+    MW_FT_NO_CONTRACT
+    float sp = 0.f, sv = 0.f;
+    for (int d = 0; d < n; ++d) {
+        const float dq = row[13 + d] - ref[13 + d];
+        const float wq = wj[d] * dq;
+        sp = fmaf(wq, dq, sp);
+        const float dv = row[13 + n + d] - ref[13 + n + d];
+        const float wv = wj[d] * dv;
+        sv = fmaf(wv, dv, sv);
+    }
+    e[kTrPose] = sp;
+    e[kTrVelocity] = sv;
+    const float dx = row[0] - ref[0], dy = row[1] - ref[1], dz = row[2] - ref[2];
+    const float xx = dx * dx;
+    const float xy = fmaf(dy, dy, xx);
+    e[kTrRootPos] = fmaf(dz, dz, xy);
+    const float ww = row[3] * qr[0];
+    const float wx = fmaf(row[4], qr[1], ww);
+    const float wy = fmaf(row[5], qr[2], wx);
+    const float dot = fmaf(row[6], qr[3], wy);
+    e[kTrRootRot] = fmaf(-dot, dot, 1.f);
+    float lin = 0.f, ang = 0.f;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float dl = row[7 + k] - ref[7 + k], da = row[10 + k] - ref[10 + k];
+        lin = fmaf(dl, dl, lin);
+        ang = fmaf(da, da, ang);
+    }
+    e[kTrRootVel] = fmaf(ang_scale, ang, lin);
+}
+
+// The five signed terms: weight_k expf(-(scale_k e_k)); 0 where the weight is
+// zero or the world diverged (its state is not finite).
+__device__ __forceinline__ void ft_track_terms(const FloatTrackF& K, const float (&e)[kTrackTerms], bool diverged,
+                                               float (&term)[kTrackTerms]) {
+    MW_FT_NO_CONTRACT
+#pragma unroll
+    for (int k = 0; k < kTrackTerms; ++k) {
+        const float x = K.scale[k] * e[k];
+        const float v = K.weight[k] * expf(-x);
+        term[k] = (K.weight[k] != 0.f && !diverged) ? v : 0.f;
+    }
+}
+// reward = r_existing + term[0] + ... + term[4], in that order
+__device__ __forceinline__ float ft_track_reward(float r_existing, const float (&term)[kTrackTerms]) {
+    MW_FT_NO_CONTRACT
+    float r = r_existing;
+#pragma unroll
+    for (int k = 0; k < kTrackTerms; ++k) r = r + term[k];
+    return r;
+}
+// Early termination: pose, root_pos or root_rot above its bound (0 = off)
+__device__ __forceinline__ bool ft_track_failed(const FloatTrackF& K, const float (&e)[kTrackTerms]) {
+    return (K.max_pose > 0.f && e[kTrPose] > K.max_pose) || (K.max_root_pos > 0.f && e[kTrRootPos] > K.max_root_pos) ||
+           (K.max_root_rot > 0.f && e[kTrRootRot] > K.max_root_rot);
 }
 
 #undef MW_FT_NO_CONTRACT

@@ -38,6 +38,37 @@ static uint32_t link_slots(const mw_sim* s, int32_t link) {
     return slots;
 }
 
+// The home row [13 + 2 n] in device memory: what init_reset starts an episode
+// from where neither a bank row nor a clip row is drawn.
+static int make_home_row(const mw_sim* s, const mw::FloatTaskF& T, mw::dev_ptr<float[]>& home) {
+    const size_t n = static_cast<size_t>(s->n), words = 13 + 2 * n;
+    std::vector<float> home_row(words, 0.f);
+    for (int k = 0; k < 7; ++k) home_row[k] = T.home_base[k];
+    for (size_t d = 0; d < n; ++d) home_row[13 + d] = T.home_q[d];
+    MW_HIP(mw::dev_alloc(home, words * sizeof(float)));
+    MW_HIP(hipMemcpy(home.get(), home_row.data(), words * sizeof(float), hipMemcpyHostToDevice));  // complete on return
+    return MW_OK;
+}
+
+// The local memory of the post launch under the task `T` a configure call is
+// about to commit, against the device's (float_env_kernel.hip).  A build of
+// this layer without the kernels (the host-only builds of the tests, whose
+// launchers do nothing) has no such function and nothing to check.
+namespace mw {
+__attribute__((weak)) hipError_t reserve_float_env_post_lds(const FloatTaskF& T, int n, int device, size_t* need,
+                                                            size_t* limit);
+}
+static int check_post_lds(const mw_sim* s, const mw::FloatTaskF& T, const char* call) {
+    if (!mw::reserve_float_env_post_lds) return MW_OK;
+    size_t need = 0, limit = 0;
+    const hipError_t err = mw::reserve_float_env_post_lds(T, s->n, s->cfg.device, &need, &limit);
+    if (need > limit)
+        return fail(MW_ECAPACITY, std::string(call) + ": the post launch would need " + std::to_string(need) +
+                                      " bytes of local memory per block, the device allows " + std::to_string(limit));
+    MW_HIP(err);
+    return MW_OK;
+}
+
 extern "C" {
 
 // Batched env of an articulated floating-base model on the wave kernel
@@ -168,6 +199,7 @@ int mw_floatenv_locomotion(mw_vecenv* e, const mw_float_loco_config* cfg, float*
     // it changes the width of the rows, which the noise amplitudes were checked against
     if (T.noise.amp || T.noise.ring)
         return fail(MW_ESTATE, "mw_floatenv_locomotion must be called before mw_floatenv_noise");
+    if (T.track.on) return fail(MW_ESTATE, "mw_floatenv_locomotion must be called before mw_floatenv_tracking");
     const float fields[] = {cfg->cmd_lo[0], cfg->cmd_lo[1], cfg->cmd_lo[2], cfg->cmd_hi[0], cfg->cmd_hi[1],
                             cfg->cmd_hi[2], cfg->cmd_zero_prob, cfg->cmd_min, cfg->action_scale, cfg->w_track_lin,
                             cfg->w_track_yaw, cfg->track_sigma, cfg->w_lin_z, cfg->w_ang_xy, cfg->w_action_rate,
@@ -338,11 +370,15 @@ int mw_floatenv_noise(mw_vecenv* e, const mw_float_noise_config* cfg, const floa
     mw::FloatTaskF& T = F.ftask;
     const size_t W = static_cast<size_t>(s->W), n = static_cast<size_t>(s->n), NO = static_cast<size_t>(T.n_obs);
     if (amplitude) {
-        // the locomotion rows end with the command (3) and the last action (n): never noisy
-        const size_t exact0 = T.loco.on ? NO - 3 - n : NO;
+        // the locomotion rows end with the command (3) and the last action (n),
+        // the tracking block follows them to the end of the row: never noisy
+        const size_t track0 = T.track.on ? static_cast<size_t>(T.track.nb) : NO;
+        const size_t exact0 = T.loco.on ? track0 - 3 - n : track0;
         for (size_t k = 0; k < NO; ++k) {
             if (!std::isfinite(amplitude[k]) || amplitude[k] < 0.f)
                 return fail(MW_EINVAL, "every noise amplitude must be finite and >= 0 (word " + std::to_string(k) + ")");
+            if (k >= track0 && amplitude[k] != 0.f)
+                return fail(MW_EINVAL, "the phase, clip and reference words take no noise (word " + std::to_string(k) + ")");
             if (k >= exact0 && amplitude[k] != 0.f)
                 return fail(MW_EINVAL, "the command and last-action words take no noise (word " + std::to_string(k) + ")");
         }
@@ -451,6 +487,12 @@ int mw_floatenv_shaping(mw_vecenv* e, const mw_float_shape_config* cfg, float* t
     const bool keep_cmd = T.action_mode == MW_FLOAT_ACTION_TORQUE &&
                           (cfg->weights[mw::kShTorque] != 0.f || cfg->weights[mw::kShPower] != 0.f || torque_out);
     MW_HIP(hipSetDevice(s->cfg.device));
+    if (T.track.on && !T.shape.on) {
+        // the shaping tiles join the tracking task's in the post launch's local memory
+        mw::FloatTaskF grown = T;
+        grown.shape.on = 1u;
+        if (int rc = check_post_lds(s, grown, "mw_floatenv_shaping")) return rc;
+    }
     mw::dev_ptr<float[]> qd, cmd, sums;
     mw::dev_ptr<int32_t[]> len;
     MW_HIP(mw::dev_alloc_zeroed(qd, nw * sizeof(float), s->stream));
@@ -531,19 +573,17 @@ int mw_floatenv_init_state(mw_vecenv* e, const mw_float_init_config* cfg, const 
     mw_sim* s = e->sim;
     mw::FloatEnv& F = *e->fenv;
     mw::FloatInitF& I = F.ftask.init;
-    if (!groups && cfg->joint_vel == 0.f && cfg->n_states == 0 && !state_dev && !draws_dev) {
+    const bool tracked = F.ftask.track.on != 0u;
+    if (tracked && cfg->n_states > 0)
+        return fail(MW_EINVAL, "a bank (n_states > 0) cannot be combined with mw_floatenv_tracking: the clips are the bank");
+    if (!tracked && !groups && cfg->joint_vel == 0.f && cfg->n_states == 0 && !state_dev && !draws_dev) {
         I = mw::FloatInitF{};  // everything off: the env as it was made
         F.d_init_home.reset();
         return MW_OK;
     }
-    const size_t n = static_cast<size_t>(s->n), words = 13 + 2 * n;
-    std::vector<float> home_row(words, 0.f);
-    for (int k = 0; k < 7; ++k) home_row[k] = F.ftask.home_base[k];
-    for (size_t d = 0; d < n; ++d) home_row[13 + d] = F.ftask.home_q[d];
     MW_HIP(hipSetDevice(s->cfg.device));
     mw::dev_ptr<float[]> home;
-    MW_HIP(mw::dev_alloc(home, words * sizeof(float)));
-    MW_HIP(hipMemcpy(home.get(), home_row.data(), words * sizeof(float), hipMemcpyHostToDevice));  // complete on return
+    if (int rc = make_home_row(s, F.ftask, home)) return rc;
     F.d_init_home = std::move(home);
     I = mw::FloatInitF{};
     I.on = 1u;
@@ -561,6 +601,119 @@ int mw_floatenv_init_state(mw_vecenv* e, const mw_float_init_config* cfg, const 
     I.states = states_dev;
     I.state_out = state_dev;
     I.draws_out = draws_dev;
+    return MW_OK;
+}
+
+// Motion-clip tracking task of a floating-base env: one more block-uniform
+// runtime branch of the post launch (float_env_kernel.hip, T.track.on) -- the
+// frame clock, the blended reference rows staged through LDS, the five errors
+// and terms, the clip-end truncation, the block of the observation -- and, in
+// its reset block, the clip row as the base row of init_reset, which this call
+// therefore turns on where mw_floatenv_init_state has not.  The clips and the
+// four outputs are the caller's; the env's own are the clip table and the joint
+// weights in device memory and every world's clip and start frame.
+static_assert(mw::kMaxClips == MW_FLOAT_MAX_CLIPS && mw::kTrackTerms == MW_FLOAT_TRACK_TERMS,
+              "the clip and term counts of float_task.hpp are the ABI's");
+int mw_floatenv_tracking(mw_vecenv* e, const mw_float_track_config* cfg, const float* clips_dev, float* terms_dev,
+                         float* errors_dev, int32_t* clip_dev, int32_t* frame_dev) {
+    if (int rc = check_configurable(e, cfg, "mw_floatenv_tracking")) return rc;
+    mw_sim* s = e->sim;
+    mw::FloatEnv& F = *e->fenv;
+    mw::FloatTaskF& T = F.ftask;
+    // it changes the width of the rows, which the noise amplitudes were checked against
+    if (T.noise.amp || T.noise.ring) return fail(MW_ESTATE, "mw_floatenv_tracking must be called before mw_floatenv_noise");
+    if (!clips_dev) return fail(MW_EINVAL, "clips_dev is null");
+    if (cfg->n_clips < 1 || cfg->n_clips > mw::kMaxClips)
+        return fail(MW_EINVAL, "n_clips must be in [1, " + std::to_string(mw::kMaxClips) + "]");
+    if (cfg->n_frames < 2) return fail(MW_EINVAL, "n_frames must be >= 2");
+    for (int c = 0; c < cfg->n_clips; ++c) {
+        if (cfg->clip_length[c] < 2)
+            return fail(MW_EINVAL, "clip " + std::to_string(c) + ": the length of a clip must be >= 2");
+        if (cfg->clip_first[c] < 0 || cfg->clip_length[c] > cfg->n_frames ||
+            cfg->clip_first[c] > cfg->n_frames - cfg->clip_length[c])
+            return fail(MW_EINVAL, "clip " + std::to_string(c) + " does not lie inside the n_frames rows of clips_dev");
+    }
+    if (cfg->frame_num < 1 || cfg->frame_den < 1) return fail(MW_EINVAL, "frame_num and frame_den must be >= 1");
+    const int n = s->n;
+    auto bad = [](float f) { return !std::isfinite(f) || f < 0.f; };
+    for (int k = 0; k < mw::kTrackTerms; ++k)
+        if (bad(cfg->weights[k]) || bad(cfg->scales[k]))
+            return fail(MW_EINVAL, "the weights and scales of mw_float_track_config must be finite and >= 0");
+    if (bad(cfg->ang_scale) || bad(cfg->max_pose) || bad(cfg->max_root_pos) || bad(cfg->max_root_rot))
+        return fail(MW_EINVAL, "ang_scale, max_pose, max_root_pos and max_root_rot must be finite and >= 0");
+    if (!(cfg->rsi_prob >= 0.f && cfg->rsi_prob <= 1.f)) return fail(MW_EINVAL, "rsi_prob must be in [0, 1]");
+    std::vector<float> wj(static_cast<size_t>(n), 1.f);
+    if (cfg->joint_weights)
+        for (int d = 0; d < n; ++d) {
+            if (bad(cfg->joint_weights[d])) return fail(MW_EINVAL, "every joint weight must be finite and >= 0");
+            wj[d] = cfg->joint_weights[d];
+        }
+    if (T.init.n_states > 0)
+        return fail(MW_EINVAL, "mw_floatenv_tracking cannot be combined with a bank of mw_floatenv_init_state (n_states > "
+                               "0): the clips are the bank");
+    // the block goes behind the rows as they are; a second call replaces the first
+    const int32_t nb = T.track.on ? T.track.nb : T.n_obs;
+    const int32_t n_obs = nb + 3 + (cfg->obs_reference ? n : 0);
+    mw::FloatTaskF grown = T;
+    grown.n_obs = n_obs;
+    grown.track.on = 1u;
+    MW_HIP(hipSetDevice(s->cfg.device));
+    if (int rc = check_post_lds(s, grown, "mw_floatenv_tracking")) return rc;
+    std::vector<int32_t> table(static_cast<size_t>(cfg->n_clips) * mw::kTrackTableWords, 0);
+    for (int c = 0; c < cfg->n_clips; ++c) {
+        table[c * mw::kTrackTableWords] = cfg->clip_first[c];
+        table[c * mw::kTrackTableWords + 1] = cfg->clip_length[c];
+        table[c * mw::kTrackTableWords + 2] = cfg->clip_loop[c] ? 1 : 0;
+    }
+    const size_t W = static_cast<size_t>(s->W);
+    mw::dev_ptr<int32_t[]> d_table, d_state;
+    mw::dev_ptr<float[]> d_wj, home;
+    MW_HIP(mw::dev_alloc(d_table, table.size() * sizeof(int32_t)));
+    MW_HIP(mw::dev_alloc(d_wj, wj.size() * sizeof(float)));
+    MW_HIP(mw::dev_alloc_zeroed(d_state, 2 * W * sizeof(int32_t), s->stream));
+    if (!T.init.on)
+        if (int rc = make_home_row(s, T, home)) return rc;
+    MW_HIP(hipMemcpy(d_table.get(), table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    MW_HIP(hipMemcpy(d_wj.get(), wj.data(), wj.size() * sizeof(float), hipMemcpyHostToDevice));  // complete on return
+    F.d_track_table = std::move(d_table);
+    F.d_track_wj = std::move(d_wj);
+    F.d_track_state = std::move(d_state);
+    if (!T.init.on) {
+        // the reset goes through init_reset: no offsets, no outputs, the home row for its pointer
+        F.d_init_home = std::move(home);
+        T.init = mw::FloatInitF{};
+        T.init.on = 1u;
+        T.init.home = F.d_init_home.get();
+        T.init.state_prob = 1.f;
+    }
+    mw::FloatTrackF& K = T.track;
+    K = mw::FloatTrackF{};
+    K.on = 1u;
+    K.n_clips = cfg->n_clips;
+    K.frame_num = cfg->frame_num;
+    K.frame_den = cfg->frame_den;
+    K.obs_reference = cfg->obs_reference ? 1 : 0;
+    K.nb = nb;
+    K.rsi_prob = cfg->rsi_prob;
+    K.ang_scale = cfg->ang_scale;
+    for (int k = 0; k < mw::kTrackTerms; ++k) {
+        K.weight[k] = cfg->weights[k];
+        K.scale[k] = cfg->scales[k];
+    }
+    K.max_pose = cfg->max_pose;
+    K.max_root_pos = cfg->max_root_pos;
+    K.max_root_rot = cfg->max_root_rot;
+    K.clips = clips_dev;
+    K.table = F.d_track_table.get();
+    K.wj = F.d_track_wj.get();
+    K.clip = F.d_track_state.get();
+    K.f0 = F.d_track_state.get() + W;
+    K.terms_out = terms_dev;
+    K.errors_out = errors_dev;
+    K.clip_out = clip_dev;
+    K.frame_out = frame_dev;
+    T.n_obs = n_obs;
+    e->task.n_obs = T.n_obs;  // mw_vecenv_obs_dim
     return MW_OK;
 }
 

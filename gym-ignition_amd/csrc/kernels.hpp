@@ -191,6 +191,12 @@ hipError_t launch_float_env_action(const struct FloatTaskF& T, const float* acti
 hipError_t launch_float_env_post(const ChainF* P, const struct FloatTaskF& T, const SimDev& S, const FreeDev& D,
                                  const VecDev& V, const float* asq, float* obs, float* reward, uint8_t* done,
                                  float* term_obs, int n, int W, int reset_all, hipStream_t st);
+// The local memory a block of the post launch would use under T (its tile of
+// rows, the shaping and tracking regions where on, the kernel's static arrays)
+// against what a block of the device may use; where that is more than the
+// default of 64 KB and fits, the kernels are told to allow it.  The configure
+// calls that grow the footprint run it before they commit (floatenv.cpp).
+hipError_t reserve_float_env_post_lds(const struct FloatTaskF& T, int n, int device, size_t* need, size_t* limit);
 
 // T_steps == 0: one step with the per-step output layout; otherwise a fused
 // open-loop rollout of T_steps steps ([T, W] inputs and outputs).

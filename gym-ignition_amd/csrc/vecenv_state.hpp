@@ -39,6 +39,12 @@ struct FloatEnv {
     dev_ptr<int32_t[]> d_shape_length;
     // initial-state randomisation (mw_floatenv_init_state): the home row [13 + 2 n]
     dev_ptr<float[]> d_init_home;
+    // motion-clip tracking (mw_floatenv_tracking): the clip table [n_clips][4],
+    // the per-joint weights [n], and clip then start frame of every world's
+    // current episode [2][W]
+    dev_ptr<int32_t[]> d_track_table;
+    dev_ptr<float[]> d_track_wj;
+    dev_ptr<int32_t[]> d_track_state;
 };
 
 }  // namespace mw

@@ -57,11 +57,20 @@ contact of chosen links, and per-episode statistics of the finished episodes
 that issues the reset: from a row of a bank of recorded states or the home
 state, plus offsets on the base pose, the base velocity and the joint
 velocities (``env.init_state``, ``env.init_draws``).
+
+``motion_clips=`` (``mw_floatenv_tracking``) makes the env a DeepMimic-style
+imitation task, again inside the same three launches: every world follows a
+clip of recorded states on an exact frame clock, its episodes start from a
+frame of a clip drawn on the device (reference-state initialisation), and the
+reward, the termination and the observation compare the state with the clip
+(``env.tracking_terms``, ``env.tracking_errors``, ``env.track_clip``,
+``env.track_frame``).
 """
 
 from __future__ import annotations
 
 import ctypes
+import fractions
 import math
 import os
 import xml.etree.ElementTree as ET
@@ -78,6 +87,10 @@ ACTION_MODES = {"torque": N.FLOAT_ACTION_TORQUE, "position": N.FLOAT_ACTION_POSI
 TASKS = ("forward", "locomotion")
 MAX_CONTACT_LINKS = 8
 # the columns of env.reward_terms, in order (mw_float_shape_config::weights)
+# the columns of env.tracking_terms and env.tracking_errors, in order (mw_float_track_config::weights)
+TRACKING_TERMS = ("pose", "velocity", "root_pos", "root_rot", "root_vel")
+TRACKING_WEIGHTS = dict(pose=0.5, velocity=0.05, root_pos=0.2, root_rot=0.15, root_vel=0.1)
+TRACKING_SCALES = dict(pose=2.0, velocity=0.1, root_pos=10.0, root_rot=5.0, root_vel=1.0, ang_scale=0.1)
 REWARD_TERMS = ("torque", "power", "joint_acc", "orientation", "base_height", "joint_limits", "collision", "stumble",
                 "contact_force", "stand_still")
 
@@ -151,7 +164,11 @@ class FloatVecEnv:
                  init_rpy_range: Optional[Sequence[Sequence[float]]] = None,
                  init_lin_vel_range: Optional[Sequence[Sequence[float]]] = None,
                  init_ang_vel_range: Optional[Sequence[Sequence[float]]] = None,
-                 init_joint_vel: Optional[float] = None):
+                 init_joint_vel: Optional[float] = None,
+                 motion_clips=None, clip_loop=False, clip_fps: Optional[float] = None,
+                 track_weights: Optional[Mapping] = None, track_scales: Optional[Mapping] = None,
+                 track_joint_weights: Optional[Sequence[float]] = None,
+                 track_termination: Optional[Mapping] = None, rsi_prob: float = 1.0, obs_reference: bool = True):
         """``model``: a shipped model's name or a URDF / SDF file.  ``home_q``
         (one value per dof) and ``home_base`` (x y z qw qx qy qz) are the reset
         state; ``pid_gains`` per dof ``(p, i, d)`` or the eight values of
@@ -312,7 +329,57 @@ class FloatVecEnv:
         roll pitch yaw (3), linear (3) and angular (3) velocity offsets, the
         bank row as a float (-1 for the home row) and the ``n`` joint-velocity
         draws; both change where, and only where, an episode ended, and are
-        ``None`` with the feature off."""
+        ``None`` with the feature off.
+
+        Motion-clip tracking (``mw_floatenv_tracking``), on when
+        ``motion_clips`` is given: a contiguous float32 tensor ``[F, 13 + 2
+        n]`` on the env's device, or a list of such tensors (at most 16), one
+        clip each, concatenated once into ``env.motion_clips``; rows in the
+        layout of ``obs[:, :13 + 2 n]``, so recorded observation rows make a
+        clip, at least 2 per clip.  The env reads the rows at every step.
+        ``clip_loop`` (one flag, or one per clip): a looping clip's last row
+        is its first pose again; it is followed round and round, the reference
+        base x and y gaining the clip's displacement at every wrap.  Its
+        heading is assumed periodic: a clip that turns over a period is not
+        followed across the wrap (heading drift is out of scope).  A clip that
+        does not loop ends the episode as truncated -- ``done`` without a
+        termination, the alive bonus kept, like the time limit -- at the first
+        step whose reference would lie beyond its last row.  ``clip_fps``: the
+        clips' frames per second (default: one frame per control step); the
+        frames per control step, ``clip_fps * step_size * steps_per_run``, must
+        be a ratio of whole numbers with a denominator of at most 1000 to
+        within 1e-9 (``ValueError`` otherwise): the frame clock is integer
+        arithmetic and never drifts; between two rows the reference is their
+        blend, the orientation by normalised linear interpolation.  Every
+        reset draws a clip and, with probability ``rsi_prob``, a start frame
+        of it (else frame 0), and starts the episode from that row; the
+        ``init_*`` offsets and ``joint_noise`` apply on top of it, and
+        ``init_states`` (a bank) is refused.  The reward gains ``weight *
+        exp(-scale * error)`` for five errors of the state against the
+        reference -- ``pose`` (sum of weighted squared joint position
+        errors, ``track_joint_weights`` per dof, default 1), ``velocity`` (the
+        same on joint velocities), ``root_pos`` (squared base position error),
+        ``root_rot`` (1 - (q . q_ref)^2), ``root_vel`` (squared base linear
+        velocity error plus ``ang_scale`` times the angular one) -- with
+        ``track_weights`` and ``track_scales`` mapping those names to values
+        (``track_scales`` also takes ``ang_scale``); names left out keep the
+        defaults of ``TRACKING_WEIGHTS`` / ``TRACKING_SCALES``.
+        ``track_termination`` maps ``pose``, ``root_pos``, ``root_rot`` to a
+        bound: the episode ends terminated, without the alive bonus, when the
+        error exceeds it.  The observation grows by a block behind everything
+        else: ``obs_slices["phase"]`` (sin and cos of 2 pi times the fraction
+        of the clip gone by), ``obs_slices["clip"]`` (the clip's index as a
+        float) and, with ``obs_reference``, ``obs_slices["reference"]``: the
+        ``n`` reference joint positions one step ahead, the target of the next
+        action.  These words take no noise.  ``env.tracking_terms`` and
+        ``env.tracking_errors`` ``[n_worlds, 5]`` hold the step's signed terms
+        and errors (``env.tracking_term_names``), ``env.track_clip`` and
+        ``env.track_frame`` ``[n_worlds]`` int32 the clip and the start frame
+        of every world's current episode; all are mirrored in ``info`` and are
+        ``None`` with the feature off.  With shaping on, ``env.episode_return``
+        includes the tracking terms.  Out of scope: end-effector or key-body
+        position terms (the post launch has no link poses), a residual action
+        around the reference, weighted clip sampling."""
         torch = _torch()
         if action_mode not in ACTION_MODES:
             raise ValueError(f"unknown action_mode {action_mode!r}; known: {sorted(ACTION_MODES)}")
@@ -373,6 +440,9 @@ class FloatVecEnv:
         self._setup_locomotion(command_ranges, cmd_interval, cmd_zero_prob, cmd_min, action_scale, w_track_lin,
                                w_track_yaw, track_sigma, w_lin_z, w_ang_xy, w_action_rate, w_air_time,
                                air_time_target, contact_force_min)
+        # ... then the tracking task, which appends its block behind the locomotion block
+        self._setup_tracking(motion_clips, clip_loop, clip_fps, track_weights, track_scales, track_joint_weights,
+                             track_termination, rsi_prob, obs_reference)
         no = ctypes.c_int32()
         N.check(N.lib().mw_vecenv_obs_dim(h, ctypes.byref(no)))
         self.obs_dim = no.value
@@ -384,6 +454,11 @@ class FloatVecEnv:
             nb = 13 + 2 * n + nl
             self.obs_slices.update(gravity=slice(nb, nb + 3), body_velocity=slice(nb + 3, nb + 9),
                                    command=slice(nb + 9, nb + 12), last_action=slice(nb + 12, nb + 12 + n))
+        if self.motion_clips is not None:
+            nt = 13 + 2 * n + nl + (12 + n if task == "locomotion" else 0)
+            self.obs_slices.update(phase=slice(nt, nt + 2), clip=slice(nt + 2, nt + 3))
+            if obs_reference:
+                self.obs_slices["reference"] = slice(nt + 3, nt + 3 + n)
         # the groups obs_noise names: the sensors behind the words
         self.noise_slices = {"base_position": slice(0, 3), "base_orientation": slice(3, 7),
                              "base_linear_velocity": slice(7, 10), "base_angular_velocity": slice(10, 13),
@@ -401,6 +476,9 @@ class FloatVecEnv:
         self._info = {"terminal_obs": self.terminal_obs}
         if self.command is not None:
             self._info["command"] = self.command
+        if self.motion_clips is not None:
+            self._info.update(tracking_terms=self.tracking_terms, tracking_errors=self.tracking_errors,
+                              track_clip=self.track_clip, track_frame=self.track_frame)
         self._setup_randomize(push_interval, push_steps, push_force, push_torque, friction_range, ground_mu)
         self._setup_inertia(mass_scale_range, payload_range, payload_box)
         self._setup_joints(joint_damping_range, joint_friction_range, effort_scale_range, joint_rand_dofs)
@@ -431,6 +509,73 @@ class FloatVecEnv:
             w_lin_z, w_ang_xy, w_action_rate, w_air_time, air_time_target, contact_force_min)
         N.check(N.lib().mw_floatenv_locomotion(self._h, ctypes.byref(lc), _ptr(self.command)),
                 "mw_floatenv_locomotion")
+
+    def _setup_tracking(self, motion_clips, clip_loop, clip_fps, track_weights, track_scales, track_joint_weights,
+                        track_termination, rsi_prob, obs_reference):
+        self.motion_clips = self.clip_table = self.clip_fraction = self.tracking_term_names = None
+        self.tracking_terms = self.tracking_errors = self.track_clip = self.track_frame = None
+        if motion_clips is None:
+            return
+        torch = _torch()
+        n, words = self.sim.dofs, 13 + 2 * self.sim.dofs
+        clips = [motion_clips] if isinstance(motion_clips, torch.Tensor) else list(motion_clips)
+        if not 1 <= len(clips) <= N.FLOAT_MAX_CLIPS:
+            raise ValueError(f"motion_clips must hold 1 to {N.FLOAT_MAX_CLIPS} clips, got {len(clips)}")
+        for c in clips:
+            if not isinstance(c, torch.Tensor) or c.device != self.device:
+                raise TypeError(f"motion_clips must be torch tensors on {self.device}")
+            if c.dtype != torch.float32 or c.dim() != 2 or c.shape[1] != words or not c.is_contiguous():
+                raise TypeError(f"every clip must be a contiguous {torch.float32} tensor of shape [F, {words}]")
+        loops = [bool(clip_loop)] * len(clips) if isinstance(clip_loop, (bool, int)) else [bool(v) for v in clip_loop]
+        if len(loops) != len(clips):
+            raise ValueError("clip_loop must be one flag or one per clip")
+        # frames per control step as an exact ratio: the device's frame clock is integer arithmetic
+        num, den = 1, 1
+        if clip_fps is not None:
+            per_step = float(clip_fps) * self.sim.step_size * self.sim.steps_per_run
+            ratio = fractions.Fraction(per_step).limit_denominator(1000)
+            if ratio <= 0 or abs(float(ratio) - per_step) > 1e-9:
+                raise ValueError(f"clip_fps {clip_fps} gives {per_step!r} frames per control step, which is no ratio of "
+                                 f"whole numbers with a denominator <= 1000 to within 1e-9")
+            num, den = ratio.numerator, ratio.denominator
+        self.clip_fraction = (num, den)
+
+        def named(given, defaults, what):
+            out = dict(defaults)
+            for name, value in (given or {}).items():
+                if name not in defaults:
+                    raise ValueError(f"{what}: unknown name {name!r}; known: {list(defaults)}")
+                out[name] = float(value)
+            return out
+        weights = named(track_weights, TRACKING_WEIGHTS, "track_weights")
+        scales = named(track_scales, TRACKING_SCALES, "track_scales")
+        bounds = named(track_termination, dict(pose=0.0, root_pos=0.0, root_rot=0.0), "track_termination")
+        wj = None
+        if track_joint_weights is not None:
+            wj = np.ascontiguousarray(track_joint_weights, dtype=np.float32)
+            if wj.shape != (n,):
+                raise ValueError(f"track_joint_weights must hold one value per dof ({n}), got shape {wj.shape}")
+        # one buffer, concatenated once; the env keeps it: the launches read it at every step
+        self.motion_clips = clips[0] if len(clips) == 1 else torch.cat(clips).contiguous()
+        lengths = [int(c.shape[0]) for c in clips]
+        firsts = [sum(lengths[:k]) for k in range(len(clips))]
+        self.clip_table = tuple(zip(firsts, lengths, loops))
+        self.tracking_term_names = TRACKING_TERMS
+        self.tracking_terms = self._zeros(self.n_worlds, N.FLOAT_TRACK_TERMS)
+        self.tracking_errors = self._zeros(self.n_worlds, N.FLOAT_TRACK_TERMS)
+        self.track_clip = self._zeros(self.n_worlds, dtype=torch.int32)
+        self.track_frame = self._zeros(self.n_worlds, dtype=torch.int32)
+        pad = [0] * (N.FLOAT_MAX_CLIPS - len(clips))
+        i16 = ctypes.c_int32 * N.FLOAT_MAX_CLIPS
+        f5 = ctypes.c_float * N.FLOAT_TRACK_TERMS
+        tc = N.MwFloatTrackConfig(
+            sum(lengths), len(clips), i16(*firsts, *pad), i16(*lengths, *pad), i16(*[int(v) for v in loops], *pad),
+            num, den, f5(*[weights[k] for k in TRACKING_TERMS]), f5(*[scales[k] for k in TRACKING_TERMS]),
+            scales["ang_scale"], bounds["pose"], bounds["root_pos"], bounds["root_rot"], rsi_prob,
+            1 if obs_reference else 0, None if wj is None else _fptr(wj))
+        N.check(N.lib().mw_floatenv_tracking(
+            self._h, ctypes.byref(tc), _ptr(self.motion_clips), _ptr(self.tracking_terms), _ptr(self.tracking_errors),
+            _ptr(self.track_clip), _ptr(self.track_frame)), "mw_floatenv_tracking")
 
     def _setup_randomize(self, push_interval, push_steps, push_force, push_torque, friction_range, ground_mu):
         self.push = self.friction = None
@@ -550,7 +695,8 @@ class FloatVecEnv:
                           init_ang_vel_range, init_joint_vel):
         self.init_states = self.init_state = self.init_draws = None
         ranges = (init_pos_range, init_rpy_range, init_lin_vel_range, init_ang_vel_range)
-        if init_states is None and init_joint_vel is None and all(r is None for r in ranges):
+        if (init_states is None and init_joint_vel is None and all(r is None for r in ranges) and
+                self.motion_clips is None):        # tracking resets through this path: its start states are reported
             return
         torch = _torch()
         n, words = self.action_dim, 13 + 2 * self.action_dim
@@ -581,7 +727,7 @@ class FloatVecEnv:
         if isinstance(obs_noise, Mapping):
             amp = np.zeros(self.obs_dim, np.float32)
             for name, value in obs_noise.items():
-                if name in ("command", "last_action"):
+                if name in ("command", "last_action", "phase", "clip", "reference"):
                     raise ValueError(f"obs_noise: the {name} words take no noise")
                 if name not in self.noise_slices:
                     raise ValueError(f"obs_noise: unknown group {name!r}; known: {sorted(self.noise_slices)}")

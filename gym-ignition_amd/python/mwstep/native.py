@@ -199,6 +199,32 @@ class MwFloatInitConfig(ctypes.Structure):
     ]
 
 
+FLOAT_MAX_CLIPS = 16
+FLOAT_TRACK_TERMS = 5
+
+
+class MwFloatTrackConfig(ctypes.Structure):
+    """mw_float_track_config (include/mwstep.h)."""
+    _fields_ = [
+        ("n_frames", ctypes.c_int32),
+        ("n_clips", ctypes.c_int32),
+        ("clip_first", ctypes.c_int32 * FLOAT_MAX_CLIPS),
+        ("clip_length", ctypes.c_int32 * FLOAT_MAX_CLIPS),
+        ("clip_loop", ctypes.c_int32 * FLOAT_MAX_CLIPS),
+        ("frame_num", ctypes.c_int32),
+        ("frame_den", ctypes.c_int32),
+        ("weights", ctypes.c_float * FLOAT_TRACK_TERMS),
+        ("scales", ctypes.c_float * FLOAT_TRACK_TERMS),
+        ("ang_scale", ctypes.c_float),
+        ("max_pose", ctypes.c_float),
+        ("max_root_pos", ctypes.c_float),
+        ("max_root_rot", ctypes.c_float),
+        ("rsi_prob", ctypes.c_float),
+        ("obs_reference", ctypes.c_int32),
+        ("joint_weights", ctypes.POINTER(ctypes.c_float)),
+    ]
+
+
 # (name, restype, argtypes) of every symbol in include/mwstep.h
 _P = ctypes.c_void_p
 _I = ctypes.c_int32
@@ -302,6 +328,7 @@ SIGNATURES = [
                                          _P, _P, _P]),
     ("mw_floatenv_shaping", ctypes.c_int, [_P, ctypes.POINTER(MwFloatShapeConfig), _P, _P, _P, _P, _P]),
     ("mw_floatenv_init_state", ctypes.c_int, [_P, ctypes.POINTER(MwFloatInitConfig), _P, _P, _P]),
+    ("mw_floatenv_tracking", ctypes.c_int, [_P, ctypes.POINTER(MwFloatTrackConfig), _P, _P, _P, _P, _P]),
 ]
 
 # include/mwscene.h

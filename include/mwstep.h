@@ -39,7 +39,9 @@ extern "C" {
 #define MW_ENOTFOUND 5   /* unknown joint / model / field name             */
 #define MW_ECAPACITY 6   /* a per-step capacity was exceeded: contact points /
                             constraint rows were dropped (the step ran without
-                            them; DART would have kept them)                */
+                            them; DART would have kept them); from
+                            mw_floatenv_tracking / _shaping: the env's tiles
+                            exceed a block's local memory, nothing changed  */
 #define MW_EDIVERGED 7   /* a world's state became non-finite in this run (the
                             run advanced every world; mw_diverged lists the
                             flagged ones) -- failure detection, SURVEY.md §5 */
@@ -889,7 +891,8 @@ int mw_floatenv_shaping(mw_vecenv* env, const mw_float_shape_config* cfg, float*
  * that must outlive the env; a world's rows are written by every reset of it.
  * MW_EINVAL: a non-finite bound or lo > hi, joint_vel < 0 or non-finite,
  * state_prob outside [0, 1], n_states < 0, n_states > 0 with states_dev NULL
- * or n_states == 0 with states_dev given. */
+ * or n_states == 0 with states_dev given, n_states > 0 on an env with
+ * mw_floatenv_tracking (whose clips are the bank). */
 typedef struct {
     float pos_lo[3], pos_hi[3];         /* m, world frame                       */
     float rpy_lo[3], rpy_hi[3];         /* rad: roll, pitch, yaw                */
@@ -901,6 +904,98 @@ typedef struct {
 } mw_float_init_config;
 int mw_floatenv_init_state(mw_vecenv* env, const mw_float_init_config* cfg, const float* states_dev, float* state_dev,
                            float* draws_dev);
+
+/* Motion-clip tracking task of a floating-base env (DeepMimic-style imitation
+ * with reference-state initialisation): every world follows a clip of recorded
+ * states on an integer frame clock, its episodes start from a drawn frame of a
+ * drawn clip, and the reward, the termination and the observation compare the
+ * state with the clip -- inside the step's three launches (no host copy,
+ * capturable).  Off unless configured, and with it off every output is what it
+ * was.  It changes the width of the rows: call it after mw_floatenv_create,
+ * after mw_floatenv_locomotion (if any), before mw_floatenv_noise and before
+ * the first mw_vecenv_reset (MW_ESTATE otherwise, or on another kind of env).
+ * A refused call leaves the env as it was.
+ *   clips    clips_dev float32 [n_frames, 13 + 2 n] is a caller-owned device
+ *            buffer that must outlive the env, rows in the layout of the first
+ *            13 + 2 n words of a row of obs (and of the bank of
+ *            mw_floatenv_init_state): recorded observation rows make a clip.
+ *            It is read through the pointer at every step and reset.  Clip c is
+ *            rows clip_first[c] .. clip_first[c] + clip_length[c] - 1, length >=
+ *            2, inside the buffer; at most MW_FLOAT_MAX_CLIPS clips.
+ *   clock    frame_num / frame_den frames per control step, both >= 1.  With f0
+ *            the start frame and t the steps taken in the episode, x_num = f0
+ *            frame_den + t frame_num; the reference of that instant x_t is row
+ *            i = x_num / frame_den blended with row i + 1 by a = (x_num %
+ *            frame_den) / frame_den (float32): integers, no drift.  Every word
+ *            is p0 + a (p1 - p0); the quaternion is blended the same way after
+ *            q1 is negated where q0 . q1 < 0, then normalised (nlerp).
+ *   loop     clip_loop[c] != 0: the period is length - 1 frames, the last row
+ *            being the first pose again; i wraps modulo the period and the
+ *            reference base x and y gain wraps (pos[last] - pos[first]).  The
+ *            heading is assumed periodic: a clip that turns over a period is
+ *            not followed across the wrap.  clip_loop[c] == 0: the episode ends
+ *            truncated -- done, not terminated, the alive bonus kept, as at the
+ *            time limit -- at the first step whose reference would need a row
+ *            beyond the last; that step is compared with the last row.
+ *   reset    a reset takes its base row from the clip where the plain reset
+ *            takes the home row, through the path of mw_floatenv_init_state: with
+ *            r the words of block 0x40000400 of the counter (global world,
+ *            episode, block, 0) mw_floatenv_randomize describes, the clip is c =
+ *            r[0] % n_clips and the start frame f0 = r[1] % (length_c - 1) where
+ *            (r[2] >> 8) 2^-24 < rsi_prob, else 0.  The offset groups of
+ *            mw_floatenv_init_state and joint_noise apply on top of the clip row
+ *            exactly as on a bank row; a bank (n_states > 0) together with
+ *            tracking is refused, whichever call comes second.
+ *   errors   the state after step t against the reference at x_t (wj the
+ *            per-joint weights, 1 where joint_weights is NULL):
+ *              0 pose      sum_d wj[d] (q_d - q^_d)^2
+ *              1 velocity  sum_d wj[d] (qd_d - qd^_d)^2
+ *              2 root_pos  |p - p^|^2
+ *              3 root_rot  1 - (q . q^)^2
+ *              4 root_vel  |v - v^|^2 + ang_scale |w - w^|^2   (world frame)
+ *            The reward gains weights[k] expf(-scales[k] e_k) per error (with
+ *            mw_floatenv_shaping the episode return includes them); a diverged
+ *            world's terms are 0.  The episode ends terminated, without the
+ *            alive bonus, where pose, root_pos or root_rot exceeds max_pose,
+ *            max_root_pos or max_root_rot (0 = off).
+ *   obs      the rows grow by a block behind everything else (after the
+ *            locomotion block where there is one): sin(2 pi phi), cos(2 pi phi),
+ *            the clip as a float, phi = x_t / (length - 1) (1 at a clip's end),
+ *            and with obs_reference != 0 the n reference joint positions at
+ *            x_{t+1}, the target of the next action.  terminal_obs carries the
+ *            finished episode's values, the reset row those of x_0 and x_1.
+ *            These words take no noise.
+ * terms_dev and errors_dev float32 [n_worlds, 5] (the step's signed terms and
+ * errors), clip_dev and frame_dev int32 [n_worlds] (the clip and the start frame
+ * of the current episode) are caller-owned device buffers (each may be NULL)
+ * that must outlive the env.
+ * MW_EINVAL: n_clips outside [1, MW_FLOAT_MAX_CLIPS], a clip shorter than 2 rows
+ * or outside [0, n_frames), frame_num or frame_den < 1, a weight, scale, bound,
+ * joint weight or ang_scale that is negative or not finite, rsi_prob outside
+ * [0, 1], clips_dev NULL, or a bank configured by mw_floatenv_init_state.
+ * MW_ECAPACITY: the post launch's tiles in local memory -- the rows of obs,
+ * the shaping tiles where on, and the 64 reference rows of this task -- exceed
+ * what a block of the device may use; nothing is changed (mw_floatenv_shaping
+ * called after this call makes the same check). */
+#define MW_FLOAT_MAX_CLIPS 16
+#define MW_FLOAT_TRACK_TERMS 5
+typedef struct {
+    int32_t n_frames;                          /* rows of clips_dev            */
+    int32_t n_clips;
+    int32_t clip_first[MW_FLOAT_MAX_CLIPS];
+    int32_t clip_length[MW_FLOAT_MAX_CLIPS];
+    int32_t clip_loop[MW_FLOAT_MAX_CLIPS];
+    int32_t frame_num, frame_den;              /* frames per control step      */
+    float weights[MW_FLOAT_TRACK_TERMS];       /* >= 0                         */
+    float scales[MW_FLOAT_TRACK_TERMS];        /* >= 0                         */
+    float ang_scale;                           /* >= 0                         */
+    float max_pose, max_root_pos, max_root_rot; /* >= 0, 0 = off               */
+    float rsi_prob;                            /* in [0, 1]                    */
+    int32_t obs_reference;
+    const float* joint_weights;                /* [n] >= 0, NULL = all 1 (host) */
+} mw_float_track_config;
+int mw_floatenv_tracking(mw_vecenv* env, const mw_float_track_config* cfg, const float* clips_dev, float* terms_dev,
+                         float* errors_dev, int32_t* clip_dev, int32_t* frame_dev);
 
 #ifdef __cplusplus
 }

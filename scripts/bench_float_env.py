@@ -79,6 +79,15 @@ env_init - env_ibase.  The two do not run the same physics after a reset (that
 is the feature), so the difference holds the run kernel's share too; the post
 launch alone is timed by float_env_trace_probe.py --init.
 
+--tracking adds env_track to the alternation: the step of another env with the
+motion-clip tracking task on (mw_floatenv_tracking: the frame clocks, the
+reference rows blended out of the clips into an LDS tile, the five errors and
+terms, 3 + n more observation words, every output buffer attached) following
+two looping clips of TRACK_FRAMES rows that hold the home state, at 2 / 3 frames
+per control step and from drawn start frames, fed the home-posture targets --
+the same physics as env -- and reports env_track - env beside the clip bytes a
+world reads per step.
+
 Not a bench.py leg.  Prints one JSON line per model."""
 
 import argparse
@@ -118,6 +127,9 @@ INIT = dict(init_pos_range=((-0.2, 0.2), (-0.2, 0.2), (0.0, 0.02)), init_rpy_ran
             init_lin_vel_range=((-0.2, 0.2), (-0.2, 0.2), (-0.05, 0.05)),
             init_ang_vel_range=((-0.2, 0.2), (-0.2, 0.2), (-0.2, 0.2)), init_joint_vel=0.2, init_state_prob=0.5)
 INIT_BANK_ROWS = 256
+# --tracking: two looping clips of the home state, a blend between two rows at most steps
+TRACK_FRAMES = 64
+TRACK = dict(clip_loop=True, rsi_prob=1.0, obs_reference=True)
 sys.path.insert(0, os.path.join(ROOT, "gym-ignition_amd", "python"))
 
 
@@ -132,6 +144,16 @@ def init_bank(torch, env, rows=INIT_BANK_ROWS, seed=0):
     bank[:, 13:13 + n] = env.home_q + rng.uniform(-0.05, 0.05, (rows, n))
     bank[:, 13 + n:] = rng.uniform(-0.1, 0.1, (rows, n))
     return torch.from_numpy(bank).to(env.device)
+
+
+def home_clips(torch, env, frames=TRACK_FRAMES):
+    """Two clips of `frames` rows on the env's device, every row the home row: following them is standing still."""
+    import numpy as np
+    n = env.action_dim
+    row = np.zeros(13 + 2 * n, np.float32)
+    row[:7] = env.home_base
+    row[13:13 + n] = env.home_q
+    return [torch.from_numpy(np.tile(row, (frames, 1))).to(env.device) for _ in range(2)]
 
 
 def capture(torch, stream, fn, warm):
@@ -260,6 +282,14 @@ def measure(torch, args, model, W):
             started.reset()
         graphs["env_ibase"] = capture(torch, stream, lambda: ibase.step_raw(actions.data_ptr()), args.warmup)
         graphs["env_init"] = capture(torch, stream, lambda: started.step_raw(actions.data_ptr()), args.warmup)
+    tracked = None
+    if args.tracking:
+        with torch.cuda.stream(stream):
+            fps = 2.0 / 3.0 / (env.sim.step_size * env.sim.steps_per_run)
+            tracked = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0, clip_fps=fps,
+                                                  motion_clips=home_clips(torch, env), **TRACK)
+            tracked.reset()
+        graphs["env_track"] = capture(torch, stream, lambda: tracked.step_raw(actions.data_ptr()), args.warmup)
     times = {k: [] for k in graphs}
     for _ in range(args.rounds):
         for k, g in graphs.items():
@@ -375,6 +405,20 @@ def measure(torch, args, model, W):
                     "init_base_z_range_after": [round(float(zs.min()), 4), round(float(zs.max()), 4)]})
         ibase.close()
         started.close()
+    if tracked is not None:
+        n = env.action_dim
+        errors = tracked.tracking_errors.cpu().numpy()
+        out.update({"env_track_step_us": round(med["env_track"], 3),
+                    "track_minus_env_us": round(med["env_track"] - med["env"], 3),
+                    "track_share_of_step": round((med["env_track"] - med["env"]) / med["env_track"], 4),
+                    "tracking": {**TRACK, "frames": TRACK_FRAMES, "clips": 2, "frames_per_step": list(tracked.clip_fraction)},
+                    "track_obs_dim": tracked.obs_dim,
+                    "track_state_equals_env_state": bool((tracked.sim.get_state() == env.sim.get_state()).all()),
+                    "track_clip_bytes_read_per_world_step": 4 * (2 * (13 + 2 * n) + 2 * n),
+                    "track_output_bytes_per_world_step": 4 * (5 + 5 + 3 + n),
+                    "track_start_frames_drawn": len(set(tracked.track_frame.cpu().numpy().tolist())),
+                    "track_largest_error": float(errors.max())})
+        tracked.close()
     env.close()
     sim.close()
     return out
@@ -403,6 +447,8 @@ def main():
     p.add_argument("--init", action="store_true",
                    help="also time envs whose worlds reset inside the windows: to the home state (env_ibase) and with "
                         "the initial-state randomisation and a 256-row bank on (env_init)")
+    p.add_argument("--tracking", action="store_true",
+                   help="also time an env that follows two looping clips of the home state (env_track)")
     p.add_argument("--task", choices=("forward", "locomotion"), default="forward",
                    help="locomotion: also time an env with the velocity-command task on (env_loco)")
     args = p.parse_args()

@@ -16,7 +16,12 @@ cost of each kernel with and without the task (profiles/float_loco/).
 --init beside the plain one: episodes of 20 steps that reset to the home state,
 and the same with the initial-state randomisation and a 256-row bank on.  Every
 20th dispatch of float_env_post_kernel of either is a launch in which all
-worlds reset (profiles/float_init/)."""
+worlds reset (profiles/float_init/).
+
+--tracking runs the env of bench_float_env.py --tracking beside the plain one:
+two looping clips of the home state followed at 2 / 3 frames per step.  Both
+post kernels are the same instance; the dispatches of the tracking env are the
+ones with the larger dynamic LDS (LDS_Block_Size in the trace)."""
 
 import os
 import sys
@@ -45,6 +50,24 @@ def init_probe(np, torch, FloatVecEnv):
             env.close()
 
 
+def tracking_probe(np, torch, FloatVecEnv):
+    from bench_float_env import TRACK, home_clips
+    for model, W in (("icub", 512), ("quadruped", 4096)):
+        plain = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0)
+        fps = 2.0 / 3.0 / (plain.sim.step_size * plain.sim.steps_per_run)
+        tracked = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0, clip_fps=fps,
+                                              motion_clips=home_clips(torch, plain), **TRACK)
+        plain.reset()
+        tracked.reset()
+        hold = torch.from_numpy(np.tile(plain.home_q, (W, 1))).to(plain.device)
+        for _ in range(300):
+            plain.step_raw(hold.data_ptr())
+            tracked.step_raw(hold.data_ptr())
+        torch.cuda.synchronize()
+        plain.close()
+        tracked.close()
+
+
 def main():
     import numpy as np
     import torch
@@ -53,6 +76,8 @@ def main():
         sys.exit("float_env_trace_probe.py needs the GPU")
     if "--init" in sys.argv[1:]:
         return init_probe(np, torch, FloatVecEnv)
+    if "--tracking" in sys.argv[1:]:
+        return tracking_probe(np, torch, FloatVecEnv)
     from bench_float_env import LOCOMOTION
     for model, W in (("icub", 512), ("quadruped", 4096)):
         plain = getattr(FloatVecEnv, model)(W, max_episode_steps=0, z_min=-10.0)
